@@ -25,6 +25,13 @@ payload / max over ranks; at N = 1 it times the shares a fixed batch gives at N 
 other_workloads also carries the fused per-SET diff-update (the north star's first op)
 and the pinned-host end-to-end path, each with its own roofline / PCIe fraction.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps
+of the metric's workload and prints the line: value, ms_per_step, the event-timed rooflines,
+the device check of the rebuilt shards.  --full adds what takes runs of its own: the
+`strong` record, the other workloads (--also), the CPU baselines and the PMC traffic lookup.
+--dump-outputs DIR writes the parities and rebuilt shards of the last timed step (a fixed
+sample of 4 KiB blocks plus every block's byte sum, dump_outputs) for build-to-build diffs.
+
 --e2e: values start and end in pinned host memory (client sockets / recovery peers):
 H2D -> kernel -> D2H pipelined over --e2e-streams HIP streams; printed as its own JSON
 line.  --e2e-zero-copy: the kernels read and write the pinned host buffers directly.
@@ -100,17 +107,24 @@ def parse(argv=None):
     ap.add_argument("--e2e-chunk", type=int, default=4096, help="stripes per pipelined chunk")
     ap.add_argument("--e2e-zero-copy", action="store_true",
                     help="--e2e with the kernels reading / writing pinned host memory directly")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the metric's workload: its strong-scaling record, the --also "
+                         "workloads, the CPU baselines and the committed PMC traffic of this "
+                         "build's kernels (a plain run times the metric's workload alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the metric's workload computed (the "
+                         "parities and the rebuilt shards) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--no-strong", action="store_true",
-                    help="skip the fixed-batch (strong scaling) record of the metric's workload")
+                    help="--full without the fixed-batch (strong scaling) record of the metric's workload")
     ap.add_argument("--harness-check", action="store_true",
                     help="run only the multi-rank harness (gloo, no GPU): launcher, shards, "
                          "barriers, max over ranks")
     ap.add_argument("--also", default="rs32_4k_lds,rs32_mixed,rs32_1m,rs42_64k,rs32_1m_recovery,"
                                       "rs32_diff_update,rs32_diff_update_lds,rs32_e2e,"
                                       "drain_host_ecmem,recovery_pool_host,set_diffs_host",
-                    help="other workloads measured after the main one, reported under "
-                         "other_workloads ('' = none)")
+                    help="other workloads measured after the main one under --full, reported "
+                         "under other_workloads ('' = none)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
                     help="wall-clock budget of the CPU-baseline thread sweep (seconds)")
     ap.add_argument("--dist-backend", default="auto", choices=["auto", "nccl", "gloo"],
@@ -123,6 +137,10 @@ def parse(argv=None):
     if bad:
         ap.error(f"--also: unknown workload(s) {bad}; choose from "
                  f"{sorted(WORKLOADS) + sorted(EXTRA_WORKLOADS)}")
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
+    if args.dump_outputs and (args.harness_check or args.e2e or args.drain or args.recovery or args.ops):
+        ap.error("--dump-outputs writes the outputs of the default (device-resident) run only")
     return args
 
 
@@ -446,8 +464,49 @@ def share_layout(stripes, lo, hi):
     return out, (out[-1][0] + out[-1][1] + 15) & ~15
 
 
-def measure_device(torch, dist, ec, world, rank, workload, args, share=None):
+DUMP_BLOCK = 4096  # bytes per sampled / summed block of a dumped arena
+DUMP_SAMPLE_BLOCKS = 512  # blocks sampled per arena (2 MiB of bytes, 8 MiB as float32)
+
+
+def dump_blocks(nblk, seed=0xC0C70010):
+    """The 4 KiB blocks of an nblk-block arena that dump_outputs samples, ascending: all of
+    them up to DUMP_SAMPLE_BLOCKS, a seeded choice of that many beyond."""
+    import numpy as np
+
+    if nblk <= DUMP_SAMPLE_BLOCKS:
+        return np.arange(nblk, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(nblk, DUMP_SAMPLE_BLOCKS, replace=False)).astype(np.int64)
+
+
+def dump_outputs(torch, out_dir, arenas, rank=0, world=1):
+    """--dump-outputs: what a caller of the timed path holds after the last timed step,
+    {name: uint8 device arena} (the M parities and the K rebuilt-shard arenas), as
+    out_dir/<name>.npy.  An arena is hundreds of MiB, so per arena two files:
+      <name>.npy        float32: DUMP_SAMPLE_BLOCKS whole 4 KiB blocks at fixed block indices
+                        (seeded, the same for every arena and every run), each byte a value
+      <name>_sum4k.npy  float64: the byte sum of every 4 KiB block of the arena, in order
+                        (all of it, the last block short), so no byte goes unseen.
+    About 45 MB for the metric's workload.  Ranks of a multi-GPU run add _rank<r>."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    for name, t in arenas.items():
+        nblk = t.numel() // DUMP_BLOCK
+        body = t[:nblk * DUMP_BLOCK].view(nblk, DUMP_BLOCK)
+        sums = [body.sum(dim=1, dtype=torch.int64)]
+        if t.numel() > nblk * DUMP_BLOCK:
+            sums.append(t[nblk * DUMP_BLOCK:].sum(dtype=torch.int64).reshape(1))
+        np.save(os.path.join(out_dir, f"{name}{tag}_sum4k.npy"), torch.cat(sums).cpu().numpy().astype(np.float64))
+        sample = body[torch.from_numpy(dump_blocks(nblk)).to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}{tag}.npy"), sample.reshape(-1).cpu().numpy().astype(np.float32))
+
+
+def measure_device(torch, dist, ec, world, rank, workload, args, share=None, dump=None):
     """Encode + rotating single-shard decode of `workload`, timed over args.steps.
+
+    dump: a directory; the parities and the rebuilt-shard arenas are written there as they
+    stand after the last timed step (dump_outputs), outside the timed region.
 
     share = (lo, hi): this rank runs only stripes [lo, hi) of the workload's batch (the
     fixed-batch split of SURVEY §8e); `value` then counts the whole batch's payload once
@@ -476,7 +535,7 @@ def measure_device(torch, dist, ec, world, rank, workload, args, share=None):
     data, parity, out = arenas[:k], arenas[k:k + m], arenas[k + m:]
     for t in data:
         t.random_(0, 256, generator=g)
-    for t in out:
+    for t in parity + out:  # (the parities too: the 16-B padding between mixed values is never written)
         t.zero_()
     masks = [ec.recovery_mask(k, m, k + p, [int(i != j) for i in range(k + m)])
              for p in range(m) for j in range(k)]
@@ -527,6 +586,11 @@ def measure_device(torch, dist, ec, world, rank, workload, args, share=None):
     enc_ms, dec_ms = sum(enc_t) / args.steps, sum(dec_t) / args.steps  # = rocprof's average
     import numpy as np
 
+    if dump:
+        named = {f"parity{p}": parity[p] for p in range(m)}
+        named.update({f"rebuilt{j}": out[j] for j in range(k)})
+        dump_outputs(torch, dump, named, rank, world)
+
     ok = True  # every shard the timed steps rebuilt equals the original (on the device)
     lost_of = [[x for x in range(k) if not (mk >> x) & 1][0] for mk in masks]
     for j in range(k):
@@ -550,9 +614,14 @@ def measure_device(torch, dist, ec, world, rank, workload, args, share=None):
     enc_gbps = enc_bytes / (enc_ms * 1e-3) / 1e9
     dec_gbps = dec_bytes / (dec_ms * 1e-3) / 1e9
     # traffic from the committed PMC summary of the engine each op ran with (the library's
-    # own report, cec_last_engine), if it measured this build's kernels
-    (enc_traffic, _), enc_stale = load_traffic(workload, engine=eng["encode"])
-    (_, dec_traffic), dec_stale = load_traffic(workload, engine=eng["decode"])
+    # own report, cec_last_engine), if it measured this build's kernels.  --full only: the
+    # comparison disassembles the library (this_code_id); a plain run reports neither.
+    if args.full:
+        (enc_traffic, _), enc_stale = load_traffic(workload, engine=eng["encode"])
+        (_, dec_traffic), dec_stale = load_traffic(workload, engine=eng["decode"])
+        code_id = this_code_id()
+    else:
+        enc_traffic = dec_traffic = enc_stale = dec_stale = code_id = None
     return {
         "k": k, "m": m, "n": n, "B": B, "what": what, "bytes_total": bytes_total, "engine": eng,
         "value": payload / elapsed / 2**30,
@@ -572,7 +641,7 @@ def measure_device(torch, dist, ec, world, rank, workload, args, share=None):
             "frac": round(enc_gbps / HBM_PEAK_GBPS, 4),
             "traffic": enc_traffic,
             "traffic_stale": enc_stale,
-            "kernel_code_id": this_code_id(),
+            "kernel_code_id": code_id,
             "kernel": f"combine_kernel<{k},{m},{'LdsEngine' if eng['encode'] == 'lds' else 'PermEngine'},"
                       "kAccNone,exact> (cec_encode)",
             "algorithmic_bytes_per_launch": enc_bytes,
@@ -1163,16 +1232,19 @@ def run_device(args):
     torch, dist, ec, world, rank = setup(args.dist_backend)
 
     set_engine(ec, args.engine)
-    r = measure_device(torch, dist, ec, world, rank, args.workload, args)
+    r = measure_device(torch, dist, ec, world, rank, args.workload, args, dump=args.dump_outputs)
+    # A plain run ends here: the metric's workload, timed.  --full adds the strong-scaling
+    # record, the --also workloads and the CPU baselines.
+    cpu_legs = args.full and not args.no_cpu_baseline
     strong = None
-    if not args.no_strong:
+    if args.full and not args.no_strong:
         torch.cuda.empty_cache()
         strong = measure_strong(torch, dist, ec, world, rank, args, r)
     # The other device-resident BASELINE configs at the same N, on the same ranks, so the
     # 1/2/4/8-GPU scaling run also covers configs[3] (RS(4,2) 64 KiB, an 8-GPU config)
     # and the north star's 1 MiB values.  `value` stays the metric's workload.
     also = {}
-    for w in [x for x in args.also.split(",") if x and x != args.workload]:
+    for w in [x for x in args.also.split(",") if args.full and x and x != args.workload]:
         torch.cuda.empty_cache()
         if w in ("rs32_diff_update", "rs32_diff_update_lds"):
             if w == "rs32_diff_update_lds":
@@ -1210,7 +1282,7 @@ def run_device(args):
         }
         if w == "rs32_4k_lds":
             also[w]["kernel"] = o["roofline"]["kernel"]
-        elif world == 1 and not args.no_cpu_baseline:
+        elif world == 1 and cpu_legs:
             # BASELINE.md §2's other CPU-baseline configs, beside the GPU number: the same
             # restated path on every CPU this process may use, over the same value sizes
             # (the mixed batch itself; 256 MiB per shard of n-byte values otherwise)
@@ -1237,6 +1309,7 @@ def run_device(args):
             "steps": args.steps,
             "warmup": args.warmup,
             "warmup_run": max(1, args.warmup),  # warmups actually run (at least one per measurement)
+            "full": bool(args.full),
             "ms_per_step": round(r["ms_per_step"], 4),
             "higher_is_better": True,
             "scaling": "weak",
@@ -1265,8 +1338,10 @@ def run_device(args):
                 p["verified"] for p in strong.get("predicted", [strong]))
         if also:
             res["other_workloads"] = also
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_legs:
             res["cpu_baseline"] = cpu_baseline(k, m, n or 4096, args.cpu_seconds)
+        if args.dump_outputs:
+            res["outputs_dumped"] = args.dump_outputs
         print(json.dumps(res), flush=True)
 
 

@@ -291,6 +291,13 @@ def test_bench_arguments():
                                       "rs32_1m_recovery", "rs32_diff_update", "rs32_diff_update_lds",
                                       "rs32_e2e", "drain_host_ecmem", "recovery_pool_host", "set_diffs_host"}
     assert not a.no_strong
+    assert a.full is False and a.dump_outputs is None  # a plain run: the metric's workload alone
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse(["--ops", "--dump-outputs", "d"])
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
     assert bench.parse(["--also="]).also == ""
     with pytest.raises(SystemExit):
         bench.parse(["--also=rs99"])
@@ -298,3 +305,38 @@ def test_bench_arguments():
     assert (a.gpus, a.steps, a.warmup) == (8, 7, 2)
     h = bench.host_cpu()
     assert h["nproc"] >= 1 and isinstance(h["model"], str)
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs' writer on host tensors: per arena a float32 sample of whole 4 KiB
+    blocks at fixed (seeded) block indices and the float64 byte sum of every block, the
+    short last one included; small arenas are written whole; the same call writes the same
+    files; ranks of a multi-GPU run get their own names."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    nblk = bench.DUMP_SAMPLE_BLOCKS + 37
+    big = torch.from_numpy(np.random.default_rng(5).integers(0, 256, nblk * 4096 + 100, dtype=np.uint8))
+    small = torch.arange(5000, dtype=torch.int64).to(torch.uint8)
+    bench.dump_outputs(torch, str(tmp_path / "a"), {"parity0": big, "rebuilt0": small})
+    idx = bench.dump_blocks(nblk)
+    assert len(idx) == bench.DUMP_SAMPLE_BLOCKS == len(set(idx.tolist())) and list(idx) == sorted(idx)
+    assert 0 <= idx[0] and idx[-1] < nblk and np.array_equal(idx, bench.dump_blocks(nblk))
+    got = np.load(tmp_path / "a" / "parity0.npy")
+    host = big.numpy()
+    assert got.dtype == np.float32 and got.shape == (bench.DUMP_SAMPLE_BLOCKS * 4096,)
+    assert np.array_equal(got.reshape(-1, 4096), host[:nblk * 4096].reshape(nblk, 4096)[idx].astype(np.float32))
+    sums = np.load(tmp_path / "a" / "parity0_sum4k.npy")
+    assert sums.dtype == np.float64 and sums.shape == (nblk + 1,)
+    assert np.array_equal(sums[:-1], host[:nblk * 4096].reshape(nblk, 4096).sum(axis=1, dtype=np.int64))
+    assert sums[-1] == host[nblk * 4096:].sum(dtype=np.int64)
+    got = np.load(tmp_path / "a" / "rebuilt0.npy")  # one whole block; the 904-byte tail is in the sums
+    assert np.array_equal(got, small.numpy()[:4096].astype(np.float32))
+    assert np.load(tmp_path / "a" / "rebuilt0_sum4k.npy").sum() == small.numpy().sum(dtype=np.int64)
+    bench.dump_outputs(torch, str(tmp_path / "b"), {"parity0": big, "rebuilt0": small})
+    for f in sorted(os.listdir(tmp_path / "a")):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    bench.dump_outputs(torch, str(tmp_path / "c"), {"parity0": small}, rank=1, world=2)
+    assert sorted(os.listdir(tmp_path / "c")) == ["parity0_rank1.npy", "parity0_rank1_sum4k.npy"]

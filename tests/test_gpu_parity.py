@@ -1116,7 +1116,7 @@ def test_bench_two_ranks_one_card_weak_and_strong(gpu):
            if x not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["CEC_BENCH_DEVICE"] = "0"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-                        "--warmup", "1", "--also=", "--no-cpu-baseline"],
+                        "--warmup", "1", "--full", "--also=", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1177,7 +1177,7 @@ def test_bench_rccl_path_one_rank(gpu):
     env = {x: v for x, v in os.environ.items()
            if x not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "CEC_BENCH_DEVICE")}
     env["CEC_BENCH_PG"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full",
                         "--also=rs32_diff_update,rs32_1m_recovery", "--no-cpu-baseline", "--dist-backend", "nccl"],
                        capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -1188,6 +1188,50 @@ def test_bench_rccl_path_one_rank(gpu):
     e = rk["per_rank"][0]
     assert e["identity"]["arch"] == "gfx950" and e["weak"]["ms_per_step"] == pytest.approx(out["ms_per_step"], rel=1e-3)
     assert set(e["other_workloads"]) == {"rs32_diff_update", "rs32_1m_recovery"}
+
+
+def test_bench_plain_run_and_output_dump(gpu, oracle, tmp_path, monkeypatch):
+    """A plain bench run's measurement (measure_device without --full) on a small batch --
+    1,030 x 4 KiB stripes, more blocks than --dump-outputs samples -- with the dump: the
+    timed steps are --steps, the line's rooflines carry no PMC lookup, and the files hold
+    what the last timed step left: the sampled parity blocks equal the oracle's encode of
+    the run's seeded inputs, every rebuilt block is the lost shard's data where that shard
+    was lost and zero elsewhere (by its byte sum), and a second run writes the same files."""
+    torch, ec = gpu
+    import bench
+
+    k, m, n, B = 3, 2, 4096, 1030
+    monkeypatch.setitem(bench.WORKLOADS, "tiny", (k, m, n, B, "test"))
+    args = bench.parse(["--steps", "2", "--warmup", "1"])
+    r = bench.measure_device(torch, None, ec, 1, 0, "tiny", args, dump=str(tmp_path / "a"))
+    assert r["verified"] is True and r["B"] == B and r["ms_per_step"] > 0 and r["value"] > 0
+    assert r["roofline"]["traffic"] is None and r["roofline"]["kernel_code_id"] is None
+    assert r["roofline"]["launch_ms"] > 0 and r["decode_roofline"]["launch_ms"] > 0
+    # the run's inputs again: same generator seed, same arenas in the same order
+    g = torch.Generator(device="cuda").manual_seed(0xC0C70002)
+    data = [t.random_(0, 256, generator=g).cpu().numpy() for t in ec.arena_tensors(k + m + k, B * n)[:k]]
+    exp = oracle.encode(ec.coding_matrix(k, m), k, m, data)
+    idx = bench.dump_blocks(B)
+    assert len(idx) == bench.DUMP_SAMPLE_BLOCKS < B
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(f"{x}{s}.npy" for x in ("parity0", "parity1", "rebuilt0", "rebuilt1", "rebuilt2")
+                           for s in ("", "_sum4k"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    for p in range(m):
+        got = np.load(tmp_path / "a" / f"parity{p}.npy")
+        assert got.dtype == np.float32
+        assert np.array_equal(got.reshape(-1, n), exp[p].reshape(B, n)[idx].astype(np.float32))
+        assert np.array_equal(np.load(tmp_path / "a" / f"parity{p}_sum4k.npy"),
+                              exp[p].reshape(B, n).sum(axis=1, dtype=np.int64).astype(np.float64))
+    for j in range(k):  # stripe s loses shard (s % 6) % 3: masks rotate over (parity, shard) pairs
+        lost = (np.arange(B) % (k * m)) % k == j
+        want = np.where(lost[:, None], data[j].reshape(B, n), 0)
+        assert np.array_equal(np.load(tmp_path / "a" / f"rebuilt{j}.npy").reshape(-1, n), want[idx].astype(np.float32))
+        assert np.array_equal(np.load(tmp_path / "a" / f"rebuilt{j}_sum4k.npy"),
+                              want.sum(axis=1, dtype=np.int64).astype(np.float64))
+    bench.measure_device(torch, None, ec, 1, 0, "tiny", args, dump=str(tmp_path / "b"))
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
 
 
 def test_graph_capture_replay(gpu, oracle):

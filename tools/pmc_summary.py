@@ -138,7 +138,7 @@ def main(out, rnd, engine="perm"):
               "w") as f:
         json.dump(traffic, f, indent=1)
     md = [f"# rocprofv3 summary ({rnd}, engine {engine})", "",
-          f"bench.py --steps 10 --warmup 2 --no-strong --engine {engine} per workload "
+          f"bench.py --steps 10 --warmup 2 --full --no-strong --engine {engine} per workload "
           "(rs32_diff_update: --also=rs32_diff_update, only its",
           "<2, 3, ..., 2> kernel counted); durations from --kernel-trace --stats;",
           "HBM bytes = 2 x FETCH_SIZE + WRITE_SIZE (KiB, gfx950 correction), separate --pmc passes.", "",

@@ -3,7 +3,7 @@
 
     python tools/trace_check.py <rocprof -d dir> <bench line .jsonl> [out.json]
 
-`tools/r06_calls.sh` runs the driver's exact command (`python bench.py`, no flags) under
+The bench command (`python bench.py`, plain or `--full`) is run under
 `rocprofv3 --kernel-trace --stats`.  The line's `roofline.launch_ms` / `decode_roofline.
 launch_ms` are the average HIP-event times of its timed whole-batch encode / decode
 launches; here the same launches are picked out of the trace -- for each op, the first
@@ -47,7 +47,7 @@ def main(prof_dir, line_path, out_path=None):
         return int(r.get("Grid_Size_X") or r.get("Grid_Size") or 0)
 
     # encode: combine_kernel<K, M, ...>; decode (one lost shard): combine_kernel<K, 1, ...>
-    out = {"command": "python bench.py (the driver's command, no flags) under rocprofv3 --kernel-trace --stats",
+    out = {"command": f"python bench.py{' --full' if line.get('full') else ''} under rocprofv3 --kernel-trace --stats",
            "whole_batch_grid_work_items": whole, "tiles": tiles, "line_value": line["value"],
            "line_kernel_code_id": line["roofline"].get("kernel_code_id"),
            "stats_csv": os.path.relpath(stats[0], prof_dir) if stats else None}
