@@ -389,8 +389,10 @@ static int pool_flush(cec_recovery_pool *p, uint8_t *const *out, bool to_host, v
                 for (int i = 0; i < c.n_in; ++i) q.coef[i] = gf_mul(inv, o.coef[i]);
                 c.outs.push_back(q);
             }
-            it = p->flush_pat.emplace(key, static_cast<int>(p->tables.pats.size())).first;
-            build_patterns({c}, 0, engine, p->tables.pats, p->tables.rows);  // (<= 2 outputs: one pattern)
+            // (<= 2 outputs: one pattern; refused before the table or the key map change)
+            const int at = static_cast<int>(p->tables.pats.size());
+            if (int rc = build_patterns({c}, 0, engine, p->tables.pats, p->tables.rows, true)) return rc;
+            it = p->flush_pat.emplace(key, at).first;
         }
         used.resize(p->tables.pats.size(), 0);
         used[it->second] = 1;

@@ -222,12 +222,16 @@ static bool has_exact(int n, int l, int acc) {
 }
 
 // Capacity kernels for every other shape (guarded, per-pattern counts and modes).
+// Returns the capacities instantiated (the launch record's nt / lt).
+struct Capacity {
+    int nt, lt;
+};
 template <class Eng>
-static void launch_generic(int nt, int lt, const CombineArgs &a, int grid, size_t lds, hipStream_t s) {
+static Capacity launch_generic(int nt, int lt, const CombineArgs &a, int grid, size_t lds, hipStream_t s) {
 #define CEC_G(NT)                                                                        \
-    if (lt <= 1) launch_k<NT, 1, Eng, kAccRuntime, false>(a, grid, lds, s);          \
-    else if (lt <= 2) launch_k<NT, 2, Eng, kAccRuntime, false>(a, grid, lds, s);     \
-    else launch_k<NT, 4, Eng, kAccRuntime, false>(a, grid, lds, s);
+    if (lt <= 1) { launch_k<NT, 1, Eng, kAccRuntime, false>(a, grid, lds, s); return {NT, 1}; }       \
+    else if (lt <= 2) { launch_k<NT, 2, Eng, kAccRuntime, false>(a, grid, lds, s); return {NT, 2}; }  \
+    else { launch_k<NT, 4, Eng, kAccRuntime, false>(a, grid, lds, s); return {NT, 4}; }
     if (nt <= 2) { CEC_G(2) }
     else if (nt <= 4) { CEC_G(4) }
     else if (nt <= 8) { CEC_G(8) }
@@ -509,6 +513,16 @@ static LaunchShape launch_shape(const std::vector<Pattern> &pats, const std::vec
 // hpats / used: the host copies of the launch's patterns and which of them its tiles
 // name (NULL: all), for the stream check below.
 enum KernelKind { kKindNarrow, kKindExact, kKindGeneric };
+static_assert(kKindNarrow == CEC_KERNEL_NARROW && kKindExact == CEC_KERNEL_EXACT &&
+                  kKindGeneric == CEC_KERNEL_GENERIC, "cec_launch_record::kind");
+static_assert(kAccNone == CEC_ACC_NONE && kAccAll == CEC_ACC_ALL && kAccAllButLast == CEC_ACC_ALL_BUT_LAST &&
+                  kAccRuntime == CEC_ACC_RUNTIME, "cec_launch_record::acc");
+static_assert(kFlagSysRelease == CEC_LAUNCH_SYS_RELEASE && kFlagWriteThrough == CEC_LAUNCH_WRITE_THROUGH,
+              "cec_launch_record::flags");
+
+// The calling thread's last enqueued kernel launch (cec_last_launch), filled by
+// launch_combine: every launch of the library goes through it.
+static thread_local cec_launch_record t_last_launch = {0, -1, 0, 0, -1, -1, 0, 0, 0, 0, 0};
 
 // Launch-time check of the argument block a kernel of `kind` is passed: every stream
 // slot a used pattern names must be one the block carries (below 2 for the narrow
@@ -576,6 +590,7 @@ static int launch_combine(int dev, const Streams &st, const uint8_t *tables, siz
     const int grid = static_cast<int>(std::min<uint64_t>(n_tiles << a.split_shift, max_wgs));
     a.grid = static_cast<uint32_t>(grid);
     bool ok;
+    Capacity cap = {sh.en, sh.el};  // exact and narrow kernels: the shape itself
     if (kind == kKindNarrow) {
         const CombineArgsN<kNarrowStreams> na = narrow_args(a);
         ok = lds ? launch_narrow<LdsEngine>(sh.eacc, na, grid, lds_bytes, stream)
@@ -584,13 +599,31 @@ static int launch_combine(int dev, const Streams &st, const uint8_t *tables, siz
         ok = lds ? launch_exact<LdsEngine>(sh.en, sh.el, sh.eacc, a, grid, lds_bytes, stream)
                  : launch_exact<PermEngine>(sh.en, sh.el, sh.eacc, a, grid, lds_bytes, stream);
     } else {
-        if (lds) launch_generic<LdsEngine>(sh.nt, sh.lt, a, grid, lds_bytes, stream);
-        else launch_generic<PermEngine>(sh.nt, sh.lt, a, grid, lds_bytes, stream);
+        cap = lds ? launch_generic<LdsEngine>(sh.nt, sh.lt, a, grid, lds_bytes, stream)
+                  : launch_generic<PermEngine>(sh.nt, sh.lt, a, grid, lds_bytes, stream);
         ok = true;
     }
     if (!ok) return fail(CEC_EINVAL, "internal: no %s kernel for %d x %d", kind == kKindNarrow ? "narrow" : "exact",
                          sh.en, sh.el);
     if (released) *released = kind == kKindNarrow && (flags & kFlagSysRelease) != 0;
+    cec_launch_record &rec = t_last_launch;
+    rec.seq += 1;
+    rec.kind = kind;
+    rec.nt = cap.nt;
+    rec.lt = cap.lt;
+    rec.acc = kind == kKindGeneric ? static_cast<int>(kAccRuntime) : sh.eacc;
+    rec.engine = lds ? CEC_ENGINE_LDS : CEC_ENGINE_PERM;
+    rec.split_shift = a.split_shift;
+    rec.flags = a.flags;
+    rec.grid = a.grid;
+    rec.n_tiles = n_tiles;
+    rec.lds_bytes = lds_bytes;
+    return CEC_OK;
+}
+
+CEC_API int cec_last_launch(cec_launch_record *out) {
+    if (!out) return fail(CEC_EINVAL, "cec_last_launch: out is NULL");
+    *out = t_last_launch;
     return CEC_OK;
 }
 
@@ -654,9 +687,21 @@ struct Combo {
 // The patterns of launch g of a combo list: outputs [4g, 4g+4) of every combo (an
 // install output is last in `outs`, so it runs in the final launch after every group
 // read old bytes), with the engine's coefficient form (and LDS rows).
-static void build_patterns(const std::vector<Combo> &combos, size_t g, int engine, std::vector<Pattern> &pats,
-                           std::vector<uint8_t> &rows) {
-    pats.reserve(combos.size());
+// This is where a Combo becomes a Pattern, so the Pattern's capacities are enforced here
+// for every caller: at most kPatN inputs, and -- for a caller that launches group g alone
+// (`only_group`: the region multiply, the pool's flush) -- no output past that group, which
+// would be dropped unsaid.  Nothing is appended on a refusal.
+static int build_patterns(const std::vector<Combo> &combos, size_t g, int engine, std::vector<Pattern> &pats,
+                          std::vector<uint8_t> &rows, bool only_group = false) {
+    for (const Combo &c : combos) {
+        if (c.n_in < 0 || c.n_in > kPatN)
+            return fail(CEC_EINVAL, "internal: a combination of %d inputs (a pattern holds %d); not launched",
+                        c.n_in, kPatN);
+        if (only_group && c.outs.size() > (g + 1) * kPatL)
+            return fail(CEC_EINVAL, "internal: a combination of %zu outputs in one launch (a pattern holds %d); "
+                                    "not launched", c.outs.size(), kPatL);
+    }
+    pats.reserve(pats.size() + combos.size());
     for (const Combo &c : combos) {
         Pattern p = blank_pattern();
         p.n_in = c.n_in;
@@ -678,6 +723,7 @@ static void build_patterns(const std::vector<Combo> &combos, size_t g, int engin
         if (engine == CEC_ENGINE_LDS) assign_rows(p, rows);
         pats.push_back(p);
     }
+    return CEC_OK;
 }
 
 // `used`: which combos the launch's tiles name (NULL = all; a persistent pattern table
@@ -693,7 +739,7 @@ static int run_combos(int dev, const Streams &st, const std::vector<Combo> &comb
     for (size_t g = 0; g < groups; ++g) {
         std::vector<Pattern> pats;
         std::vector<uint8_t> rows;
-        build_patterns(combos, g, engine, pats, rows);
+        if (int r = build_patterns(combos, g, engine, pats, rows)) return r;
         if (int r = run_combine(dev, st, pats, rows, plan, implicit_len, stream, used, engine)) return r;
     }
     return CEC_OK;
@@ -833,7 +879,7 @@ static int region_launch(int dev, const void *src, int multby, size_t n, void *d
         cb.outs.push_back(o);
         std::vector<Pattern> pats;
         std::vector<uint8_t> rows;
-        build_patterns({cb}, 0, engine, pats, rows);
+        if (int r = build_patterns({cb}, 0, engine, pats, rows, true)) return r;
         std::string k(reinterpret_cast<const char *>(pats.data()), pats.size() * sizeof(Pattern));
         k.append(reinterpret_cast<const char *>(rows.data()), rows.size());
         PatEntry *e = nullptr;
@@ -1048,6 +1094,11 @@ CEC_API int cec_residual(int k, int m, const int *matrix, int lid_self, uint32_t
     if (lid_self < k || lid_self >= k + m || !arenas || !residual || !plan)
         return fail(CEC_EINVAL, "cec_residual: bad args");
     if (int r = single_pattern_plan(plan, "cec_residual")) return r;
+    // the parity itself plus one input per data lid of the mask: a pattern holds kPatN
+    const int n_data = __builtin_popcount(mask & ((1u << k) - 1u));  // (k <= CEC_MAX_K: check_code)
+    if (1 + n_data > kPatN)
+        return fail(CEC_EINVAL, "cec_residual: mask 0x%x names %d data lids; with the parity that is more "
+                                "than the %d inputs of one combination", mask, n_data, kPatN);
     int dev;
     if (int r = current_device(&dev)) return r;
     Streams st;

@@ -107,6 +107,18 @@ class SyncRecord(ctypes.Structure):
                 ("waves_released", ctypes.c_int), ("fenced", ctypes.c_int)]
 
 
+class LaunchRecord(ctypes.Structure):
+    """cec_launch_record (cocytus_ec.h): which kernel the thread's last launch ran."""
+    _fields_ = [("seq", ctypes.c_uint64), ("kind", ctypes.c_int), ("nt", ctypes.c_int),
+                ("lt", ctypes.c_int), ("acc", ctypes.c_int), ("engine", ctypes.c_int),
+                ("split_shift", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("grid", ctypes.c_uint32),
+                ("n_tiles", ctypes.c_uint64), ("lds_bytes", ctypes.c_uint64)]
+
+
+CEC_KERNEL_NARROW, CEC_KERNEL_EXACT, CEC_KERNEL_GENERIC = 0, 1, 2
+CEC_ACC_NONE, CEC_ACC_ALL, CEC_ACC_ALL_BUT_LAST, CEC_ACC_RUNTIME = 0, 1, 2, 3
+CEC_LAUNCH_SYS_RELEASE, CEC_LAUNCH_WRITE_THROUGH = 1, 2
+
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _u32 = ctypes.c_uint32
@@ -186,6 +198,7 @@ _SIGS = {
     "cec_recovery_pool_active": ([_vp], _i),
     "cec_cache_get_info": ([ctypes.POINTER(CacheInfo)], _i),
     "cec_last_sync": ([ctypes.POINTER(SyncRecord)], _i),
+    "cec_last_launch": ([ctypes.POINTER(LaunchRecord)], _i),
     "cec_cache_set_pattern_limit": ([_i], _i),
     "cec_cache_trim": ([], _i),
     "cec_event_create": ([ctypes.POINTER(_vp)], _i),
@@ -399,6 +412,14 @@ def last_sync() -> dict:
     r = SyncRecord()
     _check(lib().cec_last_sync(ctypes.byref(r)))
     return {n: int(getattr(r, n)) for n, _ in SyncRecord._fields_}
+
+
+def last_launch() -> dict:
+    """cec_last_launch: the calling thread's last enqueued kernel launch, as a dict (kind:
+    CEC_KERNEL_*, acc: CEC_ACC_*, flags: CEC_LAUNCH_* bits; seq counts the thread's launches)."""
+    r = LaunchRecord()
+    _check(lib().cec_last_launch(ctypes.byref(r)))
+    return {n: int(getattr(r, n)) for n, _ in LaunchRecord._fields_}
 
 
 def cache_set_pattern_limit(entries: int) -> None:

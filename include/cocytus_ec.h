@@ -183,7 +183,10 @@ int cec_apply_diffs(int k, int m, const int *matrix, int lid_self, const uint8_t
 /* Recovery residual on parity lid_self (recovery.c:61-96): residual[off..] =
  * arenas[lid_self][off..] ^ sum_{data lid s in mask, s != lid_self}
  * MATRIX(lid_self, s) * arenas[s][off..].  arenas: k+m bases indexed by lid (only
- * the ones the mask names are read). */
+ * the ones the mask names are read).  Every data lid < k in the mask is one input and
+ * the parity itself is one more; a kernel combines at most 16 inputs, so a mask that
+ * names 16 data lids (k = 16 with all of them: never a recovery mask, which holds
+ * lid_self among its k lids) is refused with CEC_EINVAL and nothing is launched. */
 int cec_residual(int k, int m, const int *matrix, int lid_self, uint32_t mask,
                  const uint8_t *const *arenas, uint8_t *residual, const cec_plan *plan,
                  void *stream);
@@ -458,6 +461,34 @@ typedef struct cec_sync_record {
     int fenced;             /* a system-scope fence ran behind the op (fence event or stream sync) */
 } cec_sync_record;
 int cec_last_sync(cec_sync_record *out);
+
+/* ---- launch record (tests and diagnostics) ----
+ * Which kernel the calling thread's last enqueued launch ran, and how.  Per thread, like
+ * cec_last_sync, and for tests and diagnostics only: every op of the library runs one
+ * kernel template compiled into about a hundred kernels (narrow 1 x 1, exact shapes,
+ * capacity kernels, each for both engines), and which of them an op lands on is decided
+ * by the host -- a test that compares bytes alone cannot tell.  Filled after every
+ * successful launch; a refused or failed launch leaves it as it was.  Before the thread's
+ * first launch seq is 0 and kind / acc / engine are -1. */
+enum { CEC_KERNEL_NARROW = 0, CEC_KERNEL_EXACT = 1, CEC_KERNEL_GENERIC = 2 };
+enum { CEC_ACC_NONE = 0, CEC_ACC_ALL = 1, CEC_ACC_ALL_BUT_LAST = 2, CEC_ACC_RUNTIME = 3 };
+enum { CEC_LAUNCH_SYS_RELEASE = 1, CEC_LAUNCH_WRITE_THROUGH = 2 };
+typedef struct cec_launch_record {
+    uint64_t seq;           /* launches this thread has enqueued so far, this one included; never resets */
+    int kind;               /* CEC_KERNEL_NARROW (two-slot 1 x 1), _EXACT (shape) or _GENERIC (capacity) */
+    int nt, lt;             /* input / output counts the kernel was instantiated with: the shape
+                             * itself (narrow, exact) or the capacities chosen, {2,4,8,16} x {1,2,4} */
+    int acc;                /* read-modify-write outputs: CEC_ACC_NONE, _ALL, _ALL_BUT_LAST (exact and
+                             * narrow kernels) or _RUNTIME (capacity kernels: per pattern) */
+    int engine;             /* CEC_ENGINE_PERM or CEC_ENGINE_LDS */
+    uint32_t split_shift;   /* 2^split_shift workgroups of 256 >> split_shift lanes per tile */
+    uint32_t flags;         /* CEC_LAUNCH_* bits passed to the kernel (the LDS engine's kernels keep
+                             * non-temporal stores whatever the write-through bit says) */
+    uint32_t grid;          /* workgroups */
+    uint64_t n_tiles;
+    uint64_t lds_bytes;     /* dynamic LDS of the launch */
+} cec_launch_record;
+int cec_last_launch(cec_launch_record *out);
 
 /* ---- test hooks (host only, launch nothing themselves; not for servers) ----
  * cec_internal_check_launch_layout: the launch-time check every op's launch runs, on one

@@ -582,11 +582,15 @@ def test_failed_later_wave_leaves_nothing_in_flight(gpu, oracle, path):
             try:
                 with ec.Drainer(k, m, mat, lid_self, staging_bytes=8 << 20) as d:
                     ec.fail_launch(1)
+                    seq = ec.last_launch()["seq"]
                     with pytest.raises(ec.CecError) as e:
                         d.apply(ups, alias)
                     assert e.value.code == ec.CEC_EHIP
+                    # exactly the first wave was launched: the failure hit the second
+                    assert ec.last_launch()["seq"] == seq + 1
                     assert np.array_equal(arena, before ^ once)  # wave 0 complete on return
-                    d.apply(ups, alias)  # the whole window again: every update twice
+                    assert d.apply(ups, alias) == 2  # the whole window again: every update twice
+                    assert ec.last_launch()["seq"] == seq + 3  # (two waves, one launch each)
                     exp = before.copy()   # but the first (three times in all)
                     oracle.region_multiply(ups[0][0], c, exp[0:U], 1)
                     assert np.array_equal(arena, exp)
@@ -597,11 +601,14 @@ def test_failed_later_wave_leaves_nothing_in_flight(gpu, oracle, path):
             before = dst.copy()
             jobs = [(buf, dst.ctypes.data + addr, None, U, c, 1) for buf, addr, _ in ups]
             ec.fail_launch(1)
+            seq = ec.last_launch()["seq"]
             with pytest.raises(ec.CecError) as e:
                 ec.region_multiply_batch(jobs)
             assert e.value.code == ec.CEC_EHIP
+            assert ec.last_launch()["seq"] == seq + 1  # the first wave ran, the second failed
             assert np.array_equal(dst, before)  # nothing unpacked: no destination written
             assert ec.region_multiply_batch(jobs)[0] == 2  # two waves
+            assert ec.last_launch()["seq"] == seq + 3
             exp = before ^ once
             oracle.region_multiply(ups[0][0], c, exp[0:U], 1)
             assert np.array_equal(dst, exp)
@@ -617,13 +624,17 @@ def test_failed_later_wave_leaves_nothing_in_flight(gpu, oracle, path):
                 res0 = np.empty(once.size, np.uint8)
                 pool.residual(rid, res0)
                 ec.fail_launch(1)
+                seq = ec.last_launch()["seq"]
                 with pytest.raises(ec.CecError) as e:
                     pool.fold_updates(ups)
                 assert e.value.code == ec.CEC_EHIP
+                assert ec.last_launch()["seq"] == seq + 1  # the first wave ran, the second failed
                 res1 = np.empty(once.size, np.uint8)
                 pool.residual(rid, res1)
                 assert np.array_equal(res1, res0 ^ once)
+                seq = ec.last_launch()["seq"]
                 pool.fold_updates(ups)
+                assert ec.last_launch()["seq"] == seq + 2  # two waves, one launch each
                 res2 = np.empty(once.size, np.uint8)
                 pool.residual(rid, res2)
                 exp = res0 ^ once ^ once
