@@ -452,4 +452,133 @@ __global__ __launch_bounds__(kBlock) void combine_kernel(CombineArgsN<S> a) {
     }
 }
 
+// ---------------------------------------------------------------- the scrub kernel
+// cec_scrub: the read side of combine_kernel with every output read-modify-write, and no
+// write side.  Per tile it reads the k data streams and LT parity streams and forms the
+// syndromes S_l = P_l ^ sum_j coef[l][j] * D_j in registers.  A wave whose syndromes are
+// all zero (one ballot) ends there: no store, no atomic, a pure read stream.  Otherwise
+// (wave-uniform, rare) it reports into the tile's word:
+//   bits [0, 8)  : parity syn_shift + l has a non-zero syndrome somewhere in the wave;
+//   bits [8, 24) : data lid j cannot be the single corrupt shard: ratio[q][j] * S_0 != S_q
+//                  in some byte, for some q >= 1 (ratio[q][j] = coef[q][j] / coef[0][j]);
+// and counts the tile once (the first wave that sets a syndrome bit of the word).
+// PERM engine only: no LDS staging, no barrier.  One workgroup per (part of a) tile: the
+// host refuses a run over more tiles than one dispatch holds, so there is no grid-stride.
+constexpr int kScrubStreams = 24;  // k data slots, then the launch's parities (k + m <= 24 fit)
+
+struct ScrubArgs {
+    const uint8_t *base[kScrubStreams];  // [0, k): data; [k, k + n_out): this launch's parities
+    const Tile *tiles;                   // NULL: implicit region [0, implicit_len)
+    const Pattern *pattern;              // [0]: coefficients (n_in = k, n_out); [1]: ratio tables
+    uint32_t *words;                     // one report word per tile
+    uint32_t *counter;                   // flagged tiles
+    uint64_t implicit_len;
+    uint32_t n_tiles;
+    uint32_t split_shift;
+    uint32_t grid;
+    uint32_t syn_shift;                  // index of the launch's first parity (its syndrome bit)
+};
+
+template <int NT, int LT, bool kExact>
+__global__ __launch_bounds__(kBlock) void scrub_kernel(ScrubArgs a) {
+    const uint32_t sh = a.split_shift;
+    const uint32_t g = blockIdx.x;
+    if (g >= a.grid) return;
+    const uint32_t t = g >> sh;
+    const uint32_t part = g & ((1u << sh) - 1u);
+    const uint32_t lane = (part << (kBlockLog2 - sh)) + threadIdx.x;
+    const TileRef tr = load_tile(a, t);
+    const CEC_CONST Pattern *P = as_const(a.pattern);
+    const int n_in = kExact ? NT : P->n_in;
+    const int n_out = kExact ? LT : P->n_out;
+
+    const uint8_t *in[NT];
+    const uint8_t *par[LT];
+    uint64_t mis = 0;
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+        in[i] = nullptr;
+        if (i < n_in) {
+            in[i] = a.base[i] + tr.off;
+            mis |= reinterpret_cast<uint64_t>(in[i]);
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < LT; ++l) {
+        par[l] = nullptr;
+        if (l < n_out) {
+            par[l] = a.base[n_in + l] + tr.off;
+            mis |= reinterpret_cast<uint64_t>(par[l]);
+        }
+    }
+
+    const uint32_t pos = lane * 16;
+    if (pos >= tr.len) return;
+    const uint32_t cnt = min(16u, tr.len - pos);
+    uint4 x[NT];
+    uint4 acc[LT];
+    if ((mis & 15) == 0 && cnt == 16) {
+#pragma unroll
+        for (int i = 0; i < NT; ++i)
+            if (i < n_in) x[i] = ld16(in[i], pos);
+#pragma unroll
+        for (int l = 0; l < LT; ++l) {
+            acc[l] = make_uint4(0, 0, 0, 0);
+            if (l < n_out) acc[l] = ld16(par[l], pos);
+        }
+    } else {
+        // bytes >= cnt read 0 in every stream, so bytes past the extent never contribute
+#pragma unroll
+        for (int i = 0; i < NT; ++i)
+            if (i < n_in) x[i] = gather16(in[i], pos, cnt);
+#pragma unroll
+        for (int l = 0; l < LT; ++l) {
+            acc[l] = make_uint4(0, 0, 0, 0);
+            if (l < n_out) acc[l] = gather16(par[l], pos, cnt);
+        }
+    }
+    compute_chunk<NT, LT, PermEngine>(P, n_in, n_out, x, acc, nullptr);
+
+    uint32_t nz[LT];
+    uint32_t any = 0;
+#pragma unroll
+    for (int l = 0; l < LT; ++l) {
+        nz[l] = acc[l].x | acc[l].y | acc[l].z | acc[l].w;  // (0 for l >= n_out)
+        any |= nz[l];
+    }
+    if (__ballot(any != 0) == 0) return;  // the common case: a clean wave
+
+    uint32_t w = 0;
+#pragma unroll
+    for (int l = 0; l < LT; ++l)
+        if (l < n_out && __ballot(nz[l] != 0) != 0) w |= 1u << (a.syn_shift + l);
+    if constexpr (LT >= 2) {
+        if (n_out >= 2) {
+            const CEC_CONST Pattern *R = P + 1;
+            const PermEngine::Sel s0[4] = {PermEngine::sel(acc[0].x), PermEngine::sel(acc[0].y),
+                                           PermEngine::sel(acc[0].z), PermEngine::sel(acc[0].w)};
+#pragma unroll 1
+            for (int j = 0; j < n_in; ++j) {
+                uint32_t differ = 0;
+#pragma unroll
+                for (int q = 1; q < LT; ++q) {
+                    if (q >= n_out) continue;
+                    const CEC_CONST uint32_t *tb = R->tab[q][j];
+                    differ |= (PermEngine::mul(s0[0], tb, nullptr) ^ acc[q].x) |
+                              (PermEngine::mul(s0[1], tb, nullptr) ^ acc[q].y) |
+                              (PermEngine::mul(s0[2], tb, nullptr) ^ acc[q].z) |
+                              (PermEngine::mul(s0[3], tb, nullptr) ^ acc[q].w);
+                }
+                if (__ballot(differ != 0) != 0) w |= 1u << (8 + j);
+            }
+        }
+    }
+    // one report per wave, by its first active lane
+    const unsigned long long live = __ballot(1);
+    if (static_cast<int>(__lane_id()) == __ffsll(live) - 1) {
+        const uint32_t old = atomicOr(a.words + t, w);
+        if ((old & 0xFFu) == 0) atomicAdd(a.counter, 1u);
+    }
+}
+
 }  // namespace cec

@@ -1334,6 +1334,7 @@ CEC_API int cec_last_sync(cec_sync_record *out) {
 #include "cec_recovery.inc"
 #include "cec_pool.inc"
 #include "cec_hostbatch.inc"
+#include "cec_scrub.inc"
 
 // ============================================================== events / streams
 CEC_API int cec_event_create(void **ev) {

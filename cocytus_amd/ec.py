@@ -116,6 +116,15 @@ class LaunchRecord(ctypes.Structure):
 
 
 CEC_KERNEL_NARROW, CEC_KERNEL_EXACT, CEC_KERNEL_GENERIC = 0, 1, 2
+CEC_KERNEL_SCRUB = 3  # cec_scrub's read-only kernel
+CEC_SCRUB_UNLOCATED = -1
+
+
+class ScrubFinding(ctypes.Structure):
+    """cec_scrub_finding (cocytus_ec.h): one flagged tile of a scrub run."""
+    _fields_ = [("tile", ctypes.c_uint64), ("off", ctypes.c_uint64), ("len", ctypes.c_uint32),
+                ("syndromes", ctypes.c_uint32), ("ruled_out", ctypes.c_uint32), ("lid", ctypes.c_int32)]
+
 CEC_ACC_NONE, CEC_ACC_ALL, CEC_ACC_ALL_BUT_LAST, CEC_ACC_RUNTIME = 0, 1, 2, 3
 CEC_LAUNCH_SYS_RELEASE, CEC_LAUNCH_WRITE_THROUGH = 1, 2
 
@@ -196,6 +205,15 @@ _SIGS = {
     "cec_recovery_pool_residual": ([_vp, _i, _vp, _vp], _i),
     "cec_recovery_pool_end": ([_vp, _i], _i),
     "cec_recovery_pool_active": ([_vp], _i),
+    "cec_scrub_create": ([ctypes.POINTER(_vp), ctypes.c_uint64], _i),
+    "cec_scrub_destroy": ([_vp], _i),
+    "cec_scrub_release_stream": ([_vp, _vp], _i),
+    "cec_scrub": ([_vp, _i, _i, _ip, _pp, _pp, _vp, _vp], _i),
+    "cec_scrub_region": ([_vp, _i, _i, _ip, _pp, _pp, ctypes.c_size_t, _vp], _i),
+    "cec_scrub_wait": ([_vp], ctypes.c_int64),
+    "cec_scrub_findings": ([_vp, ctypes.POINTER(ScrubFinding), _i], _i),
+    "cec_scrub_classify": ([_u32, _i, _i, _ip], _i),
+    "cec_scrub_repair": ([_vp, _i, _i, _ip, _pp, _pp, _vp, _ip], _i),
     "cec_cache_get_info": ([ctypes.POINTER(CacheInfo)], _i),
     "cec_last_sync": ([ctypes.POINTER(SyncRecord)], _i),
     "cec_last_launch": ([ctypes.POINTER(LaunchRecord)], _i),
@@ -816,6 +834,80 @@ class RecoveryPool:
                 _lib.cec_recovery_pool_destroy(self._h)
         except Exception:
             pass
+
+
+class Scrub:
+    """cec_scrub_report: a reusable report for scrub runs of up to max_tiles tiles -- does
+    parity still match data, and if not, in which 4 KiB tiles and which shard (cocytus_ec.h).
+    All k + m arenas must be on the device.  The plan of a run must outlive findings() /
+    repair()."""
+
+    def __init__(self, max_tiles: int):
+        self._h = ctypes.c_void_p()
+        _check(lib().cec_scrub_create(ctypes.byref(self._h), max_tiles))
+
+    def run(self, k, m, matrix, data, parity, plan: Plan, stream=None) -> None:
+        """cec_scrub: async on stream; wait() returns the flagged tiles."""
+        _check(lib().cec_scrub(self._h, k, m, _int_array(matrix), _ptr_array(data), _ptr_array(parity),
+                               plan.handle, _stream(stream)))
+
+    def run_region(self, k, m, matrix, data, parity, length: int, stream=None) -> None:
+        _check(lib().cec_scrub_region(self._h, k, m, _int_array(matrix), _ptr_array(data),
+                                      _ptr_array(parity), length, _stream(stream)))
+
+    def wait(self) -> int:
+        n = lib().cec_scrub_wait(self._h)
+        if n < 0:
+            _check(int(n))
+        return int(n)
+
+    def findings(self, cap: int | None = None) -> list[dict]:
+        """The flagged tiles of the last run, ascending: dicts of cec_scrub_finding's fields."""
+        if cap is None:
+            cap = self.wait()
+        arr = (ScrubFinding * max(cap, 1))()
+        n = lib().cec_scrub_findings(self._h, arr, cap)
+        if n < 0:
+            _check(n)
+        return [{f: int(getattr(arr[i], f)) for f, _ in ScrubFinding._fields_} for i in range(n)]
+
+    def repair(self, k, m, matrix, data, parity, stream=None) -> int:
+        """cec_scrub_repair: rebuild every located finding in place; returns the findings
+        left alone (unlocated)."""
+        left = ctypes.c_int()
+        _check(lib().cec_scrub_repair(self._h, k, m, _int_array(matrix), _ptr_array(data),
+                                      _ptr_array(parity), _stream(stream), ctypes.byref(left)))
+        return int(left.value)
+
+    def release_stream(self, stream) -> None:
+        _check(lib().cec_scrub_release_stream(self._h, _stream(stream)))
+
+    def destroy(self) -> None:
+        if self._h:
+            _check(lib().cec_scrub_destroy(self._h))
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.destroy()
+
+    def __del__(self):
+        try:
+            if self._h and _lib is not None:
+                _lib.cec_scrub_destroy(self._h)
+        except Exception:
+            pass
+
+
+def scrub_classify(word: int, k: int, m: int, matrix) -> int:
+    """cec_scrub_classify (host only): the corrupt lid of a report word (syndromes |
+    ruled_out << 8) or CEC_SCRUB_UNLOCATED; a word without a syndrome bit raises."""
+    rc = lib().cec_scrub_classify(word, k, m, _int_array(matrix))
+    if rc < 0 and lib().cec_last_error():  # (a verdict leaves no message, an error does)
+        _check(rc)
+    return rc
 
 
 def pool_replies(ids, peer_lids, units) -> tuple:

@@ -16,7 +16,7 @@
  * (/root/reference/const.h:26).  Unaligned offsets and lengths are accepted
  * (slower byte path for the affected tiles), bit-exact either way.
  *
- * LIFETIME RULE (every object: plan, drainer, recovery session, recovery pool):
+ * LIFETIME RULE (every object: plan, drainer, recovery session, recovery pool, scrub report):
  * destroy the object BEFORE any stream it was used on.  An object records the streams
  * its calls used and its destroy synchronises exactly those (never the whole device);
  * a handle of a destroyed stream cannot be synchronised (it crashes the HIP runtime).
@@ -231,8 +231,13 @@ int cec_drainer_release_stream(cec_drainer *d, void *stream);   /* LIFETIME RULE
 
 /* parity[addr..] ^= MATRIX(lid_self, src_lid) * buf for every update, as the sequential
  * loop of memcached.c:7762-7767 would leave it (XOR accumulation commutes; updates
- * whose ranges overlap are put in separate launches, never raced).  Synchronous: on
- * return every update is applied and the host buffers may be reused / acked. */
+ * whose ranges overlap are put in separate launches, never raced).  Synchronous: on a
+ * CEC_OK return every update is applied and the host buffers may be reused / acked.
+ * On CEC_EHIP the launches of earlier overlap waves or rounds may already be applied and
+ * the later ones not, and a retry would apply the earlier ones twice: the parity arena is
+ * then inconsistent in some 4 KiB units of the window's ranges.  Where every arena of the
+ * group is on this device, cec_scrub + cec_scrub_repair over those ranges find and rebuild
+ * them (below); otherwise the process must stop. */
 int cec_drainer_apply(cec_drainer *d, const cec_host_update *updates, int n,
                       uint8_t *parity, void *stream);
 
@@ -420,6 +425,83 @@ int cec_recovery_pool_residual(cec_recovery_pool *pool, int id, void *dst, void 
 int cec_recovery_pool_end(cec_recovery_pool *pool, int id);
 int cec_recovery_pool_active(const cec_recovery_pool *pool);
 
+/* ---- scrub: is the group still consistent, and if not, where? ----
+ * The ops above produce parity and rebuild shards the caller knows are lost.  cec_scrub
+ * asks the device whether parity still matches data: per 4 KiB tile of a plan (or of
+ * [0, len)) it reads the k data and m parity streams, forms the syndromes
+ * S_p = parity[p] ^ sum_j MATRIX(k+p, j) * data[j] in registers and writes NOTHING to the
+ * arenas; a clean wave touches no memory but its inputs.  Where a syndrome is non-zero the
+ * tile is flagged, counted once, and the wave records which data lids it can rule out as
+ * the single corrupt shard (lid j is ruled out where MATRIX(k+q, j) / MATRIX(k+p0, j) * S_p0
+ * != S_q in some byte, for the parities p0, q of one launch; m > 4 runs one launch per four
+ * parities, and a launch of one parity rules out nothing).
+ *
+ * PLACEMENT: a cross-shard scrub needs all k + m arenas of the group on this device
+ * (DESIGN.md §3's single-GPU placement).  A process that holds only its own shard cannot
+ * scrub alone.  Where the server would call it: the idle loop (idle_event_handler,
+ * memcached.c:5712-5734), over the arenas in idle time; and after a CEC_EHIP from
+ * cec_drainer_apply / cec_recovery_pool_fold_updates, over the window's ranges, instead of
+ * stopping.
+ *
+ * ENGINE: always PERM, whatever cec_set_engine says (no LDS staging, no barrier; the two
+ * engines are within 2 % on every 4 KiB op); cec_last_engine() reports PERM.
+ *
+ * ASSUMPTION: a located lid is exact when at most one lid is corrupt in the tile.  With
+ * two or more the verdict is CEC_SCRUB_UNLOCATED or, improbably, a wrong lid, as with any
+ * syndrome decoder.  m = 1 detects but never locates.  The location rests on the MDS
+ * property of the matrices reed_sol_big_vandermonde_distribution_matrix returns: non-zero
+ * parity coefficients whose ratios between two parity rows differ from column to column.
+ *
+ * A cec_scrub_report is reusable (device words + counter, pinned mirror) for runs of up to
+ * max_tiles tiles; at most 0xFFFFFFFF / 256 tiles (64 GiB per arena), one dispatch.  (The
+ * type is not named cec_scrub: C keeps typedefs and functions in one namespace.)  Calls on
+ * one report must not overlap.  LIFETIME RULE (top): destroy waits for the streams the
+ * report was used on, only.  The report keeps no pointer of a run but the plan, which must
+ * outlive cec_scrub_findings / cec_scrub_repair.  Not for use inside a stream capture. */
+typedef struct cec_scrub_report cec_scrub_report;
+#define CEC_SCRUB_UNLOCATED (-1)
+typedef struct cec_scrub_finding {
+    uint64_t tile;        /* index into the run's tile list */
+    uint64_t off;         /* arena offset of the tile's bytes */
+    uint32_t len;         /* 1..4096 */
+    uint32_t syndromes;   /* bit p: parity p's syndrome is non-zero in this tile */
+    uint32_t ruled_out;   /* bit j: data lid j cannot be the single corrupt shard */
+    int32_t  lid;         /* the corrupt lid (data 0..k-1, parity k..k+m-1) or CEC_SCRUB_UNLOCATED */
+} cec_scrub_finding;
+
+int cec_scrub_create(cec_scrub_report **out, uint64_t max_tiles);
+int cec_scrub_destroy(cec_scrub_report *s);                /* LIFETIME RULE: waits for its streams only */
+int cec_scrub_release_stream(cec_scrub_report *s, void *stream);
+/* Async on `stream`: clear the report, launch, copy the counter back.  Checked as cec_encode
+ * checks (code, NULL arenas, the plan's device, extent patterns must be 0); in addition
+ * every data AND parity base is needed (a lost parity cannot be checked: CEC_EINVAL), and a
+ * run of more tiles than the report holds is CEC_EINVAL.  A failed run leaves the report
+ * invalid: wait / findings / repair return CEC_EINVAL until the next successful run. */
+int cec_scrub(cec_scrub_report *s, int k, int m, const int *matrix, const uint8_t *const *data,
+              const uint8_t *const *parity, const cec_plan *plan, void *stream);
+int cec_scrub_region(cec_scrub_report *s, int k, int m, const int *matrix, const uint8_t *const *data,
+                     const uint8_t *const *parity, size_t len, void *stream);
+/* Synchronises the run's stream (never the device): flagged tiles (>= 0) or a negative cec_status. */
+int64_t cec_scrub_wait(cec_scrub_report *s);
+/* After the run (waits if cec_scrub_wait has not): up to cap findings, ascending tile; returns
+ * the number written.  The per-tile words are copied back only when the counter is non-zero. */
+int cec_scrub_findings(cec_scrub_report *s, cec_scrub_finding *out, int cap);
+/* Host only.  word = syndromes | ruled_out << 8.  With exactly one syndrome bit p (m >= 2):
+ * parity lid k + p.  With the syndrome bits of every parity whose coefficient for j is
+ * non-zero (all m for an MDS matrix) and j the only data lid not ruled out: j.  Anything
+ * else (every finding when m = 1, two lids corrupt in one tile) is CEC_SCRUB_UNLOCATED,
+ * with an empty cec_last_error().  A word without a syndrome bit, or a bad code, is
+ * CEC_EINVAL (the same value: cec_last_error() then holds a message). */
+int cec_scrub_classify(uint32_t word, int k, int m, const int *matrix);
+/* Rebuild every located finding of the last run in place, with the existing ops: one
+ * cec_decode over the tiles of located data lids (per lost lid j the mask is every lid but
+ * j, led by the first parity, as cec_recovery_mask builds it; out[j] is the data arena
+ * itself), one cec_encode per located parity.  Unlocated findings are left untouched and
+ * counted into *unrepaired.  Returns after the rebuilds completed on `stream`.  Run
+ * cec_scrub again to confirm. */
+int cec_scrub_repair(cec_scrub_report *s, int k, int m, const int *matrix, uint8_t *const *data,
+                     uint8_t *const *parity, void *stream, int *unrepaired);
+
 /* ---- process-wide caches ----
  * Coefficient tables are uploaded once per distinct content (asynchronously, on the
  * caller's stream; another stream waits on the upload event) and kept in an LRU cache
@@ -470,7 +552,9 @@ int cec_last_sync(cec_sync_record *out);
  * by the host -- a test that compares bytes alone cannot tell.  Filled after every
  * successful launch; a refused or failed launch leaves it as it was.  Before the thread's
  * first launch seq is 0 and kind / acc / engine are -1. */
-enum { CEC_KERNEL_NARROW = 0, CEC_KERNEL_EXACT = 1, CEC_KERNEL_GENERIC = 2 };
+enum { CEC_KERNEL_NARROW = 0, CEC_KERNEL_EXACT = 1, CEC_KERNEL_GENERIC = 2,
+       CEC_KERNEL_SCRUB = 3 /* cec_scrub's read-only kernel: nt = k or its capacity {4,8,16}, lt = the
+                             * launch's parities or their capacity {1,2,4}, acc = CEC_ACC_ALL, PERM */ };
 enum { CEC_ACC_NONE = 0, CEC_ACC_ALL = 1, CEC_ACC_ALL_BUT_LAST = 2, CEC_ACC_RUNTIME = 3 };
 enum { CEC_LAUNCH_SYS_RELEASE = 1, CEC_LAUNCH_WRITE_THROUGH = 2 };
 typedef struct cec_launch_record {
