@@ -202,6 +202,19 @@ static int drain_bail(hipStream_t s, int rc) {
     return rc;
 }
 
+// The fold launches of one round, one per overlap wave: `spans` are the waves' tile ranges
+// in the round's tile list (dt on the device, ht the same tiles on the host).
+static int drainer_fold(cec_drainer *d, int dev, const Streams &st, const std::vector<Combo> &combos, const Tile *dt,
+                        const Tile *ht, const std::vector<std::pair<size_t, size_t>> &spans, hipStream_t s) {
+    for (const auto &sp : spans) {
+        if (sp.second == sp.first) continue;
+        const TileSource wave = TileSource::window(dt + sp.first, ht + sp.first, sp.second - sp.first);
+        if (int r = run_combos(dev, st, combos, wave, s)) return drain_bail(s, r);
+        ++d->last_launches;
+    }
+    return CEC_OK;
+}
+
 // All updates already inside the pinned staging area: no pack copy.  The caller has
 // enqueued the H2D of the used span; the fold launches wave by wave (tile lists in
 // rounds of the tile buffer's capacity).
@@ -232,16 +245,7 @@ static int drainer_apply_in_place(cec_drainer *d, const cec_host_update *u,
             ++next;
         }
         HIP_TRY(hipMemcpyAsync(d->d_tiles, d->h_tiles, nt * sizeof(Tile), hipMemcpyHostToDevice, s));
-        for (const auto &sp : spans) {
-            if (sp.second == sp.first) continue;
-            cec_plan pl;
-            pl.device = dev;
-            pl.d_tiles = d->d_tiles + sp.first;
-            pl.n_tiles = static_cast<int64_t>(sp.second - sp.first);
-            pl.n_line_tiles = count_line_tiles(d->h_tiles + sp.first, sp.second - sp.first);
-            if (int r = run_combos(dev, st, combos, &pl, 0, s)) return drain_bail(s, r);
-            ++d->last_launches;
-        }
+        if (int r = drainer_fold(d, dev, st, combos, d->d_tiles, d->h_tiles, spans, s)) return r;
         HIP_TRY(hipStreamSynchronize(s));  // the pinned tile list is reused by the next round
     }
     return CEC_OK;
@@ -286,16 +290,7 @@ static int drainer_apply_small(cec_drainer *d, const cec_host_update *u, const s
     Streams st;
     st.base[0] = d->sm_d;
     st.base[1] = parity;
-    for (const auto &sp : spans) {
-        if (sp.second == sp.first) continue;
-        cec_plan pl;  // view of the mapped tile list
-        pl.device = dev;
-        pl.d_tiles = d->smt_d + sp.first;
-        pl.n_tiles = static_cast<int64_t>(sp.second - sp.first);
-        pl.n_line_tiles = count_line_tiles(d->smt_h + sp.first, sp.second - sp.first);
-        if (int r = run_combos(dev, st, combos, &pl, 0, s)) return drain_bail(s, r);
-        ++d->last_launches;
-    }
+    if (int r = drainer_fold(d, dev, st, combos, d->smt_d, d->smt_h, spans, s)) return r;
     hipPointerAttribute_t at;  // the arena in host memory (registered): fence the results
     bool host = true;
     if (hipPointerGetAttributes(&at, parity) == hipSuccess)
@@ -503,18 +498,9 @@ CEC_API int cec_drainer_apply(cec_drainer *d, const cec_host_update *u, int n, u
         Streams st;
         st.base[0] = d->d_stage;  // tiles carry src_off relative to the whole staging area
         st.base[1] = parity;
-        for (const auto &sp : spans) {
-            if (sp.second == sp.first) continue;
-            cec_plan pl;  // view of the drainer's reusable tile buffer
-            pl.device = dev;
-            pl.d_tiles = d->d_tiles + h * d->tile_half + sp.first;
-            pl.n_tiles = static_cast<int64_t>(sp.second - sp.first);
-            pl.n_line_tiles = count_line_tiles(ht + sp.first, sp.second - sp.first);
-            if (int r = run_combos(dev, st, combos, &pl, 0, s)) {
-                d->pending[0] = d->pending[1] = false;
-                return drain_bail(s, r);
-            }
-            ++d->last_launches;
+        if (int r = drainer_fold(d, dev, st, combos, d->d_tiles + h * d->tile_half, ht, spans, s)) {
+            d->pending[0] = d->pending[1] = false;
+            return r;
         }
         h ^= 1;
     }

@@ -611,12 +611,8 @@ CEC_API int cec_region_multiply_batch(const cec_region_job *jobs, int n, void *s
                                  : rd.any_base ? stage_dev + rd.dseg + rd.sseg : stage_dev + rd.dseg;  // B staged
         for (int w = 0; w < max_wave; ++w) {
             if (span[w + 1] == span[w]) continue;
-            cec_plan pl;  // view of the context's tile buffer
-            pl.device = dev;
-            pl.d_tiles = dt + span[w];
-            pl.n_tiles = static_cast<int64_t>(span[w + 1] - span[w]);
-            pl.n_line_tiles = count_line_tiles(ht + span[w], span[w + 1] - span[w]);
-            if (int r = run_combos(dev, st, rd.in_place ? combos_ip : combos, &pl, 0, s)) return r;
+            const TileSource wave = TileSource::window(dt + span[w], ht + span[w], span[w + 1] - span[w]);
+            if (int r = run_combos(dev, st, rd.in_place ? combos_ip : combos, wave, s)) return r;
             ++hb.last_launches;
             hb.last_in_place += rd.in_place;
         }

@@ -415,13 +415,10 @@ static int pool_flush(cec_recovery_pool *p, uint8_t *const *out, bool to_host, v
         if (out) st.base[2 + k + j] = out[j];
     }
     if (to_host) st.base[2 + k] = p->out_dev;
-    cec_plan pl;  // view of the pool's tile buffer
-    pl.device = dev;
-    pl.d_tiles = p->d_tiles;
-    pl.n_tiles = static_cast<int64_t>(nt);
-    pl.n_line_tiles = pl.n_tiles;  // whole 4 KiB units on 4 KiB offsets
-    if (int rc = launch_combine(dev, st, p->tables.d, p->tables.cap_pats, launch_shape(p->tables.pats, &used),
-                                engine == CEC_ENGINE_LDS, &pl, 0, nt, s, p->tables.pats.data(), &used))
+    // (the pool's tile buffer: whole 4 KiB units on 4 KiB offsets)
+    if (int rc = launch_combine(dev, st, Tables{p->tables.d, p->tables.cap_pats, p->tables.pats.data(), &used},
+                                launch_shape(p->tables.pats, &used), engine == CEC_ENGINE_LDS,
+                                TileSource::whole_units(p->d_tiles, nt), s))
         return rc;
     HIP_TRY(hipGetLastError());
     // tile buffer and staging reusable; rebuilt shards visible if out is host memory
@@ -520,11 +517,6 @@ CEC_API int cec_recovery_pool_fold_update(cec_recovery_pool *p, int peer, uint64
         memcpy(p->diff_host, diff, len);
         d = p->diff_dev;
     }
-    cec_plan pl;
-    pl.device = dev;
-    pl.d_tiles = p->d_tiles;
-    pl.n_tiles = static_cast<int64_t>(nt);
-    pl.n_line_tiles = count_line_tiles(p->h_tiles, nt);
     const int k = p->k;
     const int *matrix = p->matrix.data();
     Streams st;
@@ -539,7 +531,7 @@ CEC_API int cec_recovery_pool_fold_update(cec_recovery_pool *p, int peer, uint64
     o.mode = kModeXor;
     o.coef[0] = MATRIX(p->lid_self, peer);  // recovery.c:123
     c.outs.push_back(o);
-    if (int rc = run_combos(dev, st, {c}, &pl, 0, s)) return rc;
+    if (int rc = run_combos(dev, st, {c}, TileSource::window(p->d_tiles, p->h_tiles, nt), s)) return rc;
     if (int rc = stream_wait(s, false)) return rc;  // (the residual is in HBM)
     return units;
 }
@@ -688,12 +680,8 @@ CEC_API int cec_recovery_pool_fold_updates(cec_recovery_pool *p, const cec_host_
     st.base[1] = p->residual;
     int rc = CEC_OK;
     for (size_t w = 0; w < nw && !rc; ++w) {
-        cec_plan pl;
-        pl.device = dev;
-        pl.d_tiles = d + wave_start[w];
-        pl.n_tiles = static_cast<int64_t>(wave_start[w + 1] - wave_start[w]);
-        pl.n_line_tiles = count_line_tiles(h + wave_start[w], wave_start[w + 1] - wave_start[w]);
-        rc = run_combos(dev, st, combos, &pl, 0, s, &used);
+        const size_t lo = wave_start[w], n_wave = wave_start[w + 1] - lo;
+        rc = run_combos(dev, st, combos, TileSource::window(d + lo, h + lo, n_wave), s, &used);
     }
     if (!rc) rc = stream_wait(s, false);  // (the residual is in HBM; staging and tiles reusable)
     if (rc) {  // an earlier wave may still read the diff staging and the tiles (the pool's own
@@ -768,12 +756,8 @@ static int pool_solve(cec_recovery_pool *p, const int *ids, int n, uint8_t *cons
                            static_cast<uint64_t>(r->slot) * kTile, static_cast<uint32_t>(r->nunits) * kTile,
                            static_cast<uint32_t>(lost[0]));
     }
-    cec_plan pl;
-    pl.device = dev;
-    pl.d_tiles = p->d_tiles;
-    pl.n_tiles = static_cast<int64_t>(nt);
-    pl.n_line_tiles = pl.n_tiles;
-    if (int rc = run_combos(dev, st, combos, &pl, 0, s, &used)) return rc;
+    // (whole 4 KiB units on 4 KiB offsets, as the flush's)
+    if (int rc = run_combos(dev, st, combos, TileSource::whole_units(p->d_tiles, nt), s, &used)) return rc;
     if (int rc = stream_wait(s, to_host || any_host_memory(out, p->k))) return rc;
     for (int x = 0; x < n; ++x) {
         p->reqs[ids[x]].solved = true;

@@ -254,7 +254,7 @@ CEC_API int cec_recovery_add_peer(cec_recovery *r, int peer, const void *units, 
         o.mode = kModeXor;
     }
     c.outs.push_back(o);
-    if (int rc = run_combos(dev, st, {c}, nullptr, r->nbuf, s)) return rc;
+    if (int rc = run_combos_region(dev, st, {c}, r->nbuf, s)) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     r->touched = true;
     r->contributed |= 1u << peer;
@@ -360,7 +360,7 @@ CEC_API int cec_recovery_solve(cec_recovery *r, const void *const *peer_residual
         for (int j = 0; j < n; ++j) q.coef[j] = inv[x * n + j];
         c.outs.push_back(q);
     }
-    if (int rc = run_combos(dev, st, {c}, nullptr, r->nbuf, s)) { cleanup(); return rc; }
+    if (int rc = run_combos_region(dev, st, {c}, r->nbuf, s)) { cleanup(); return rc; }
     for (auto &dl : downloads)
         if (int rc = r->stager.download(dl.first, dl.second, r->nbuf, s)) { cleanup(); return rc; }
     // Synchronous (cocytus_ec.h): out, device or pinned, holds the rebuilt bytes on return,
@@ -483,7 +483,7 @@ CEC_API int cec_recovery_finish(cec_recovery *r, int peer, const void *units,
         if (j != self) st.base[2 + j] = const_cast<uint8_t *>(C[j]);
     st.base[2 + CEC_MAX_M] = r->residual;
     for (int x = 0; x < n; ++x) st.base[3 + CEC_MAX_M + x] = dout[x];
-    if (int rc = run_combos(dev, st, {cb}, nullptr, r->nbuf, s)) { cleanup(); return rc; }
+    if (int rc = run_combos_region(dev, st, {cb}, r->nbuf, s)) { cleanup(); return rc; }
     // Synchronous (cocytus_ec.h): the rebuilt bytes are in out on return, and units /
     // peer residuals may be reused by the caller.
     const int rc = stream_wait(s, any_host_memory(reinterpret_cast<uint8_t *const *>(out), k));

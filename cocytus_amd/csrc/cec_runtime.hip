@@ -192,9 +192,17 @@ static bool launch_narrow(int acc, const CombineArgsN<kNarrowStreams> &a, int gr
     return true;
 }
 
-// Exact-shape kernels for the hot ops: encode / decode / residual / solve (no RMW,
+// The exact shapes (n_in, n_out, acc), X(N, L, A) for each -- the one list launch_exact's
+// kernels and has_exact are both made from: encode / decode / residual / solve (no RMW,
 // up to 8 inputs x 4 outputs), parity apply and region multiply-XOR (1 x 1 RMW),
 // diff-update (2 inputs, M parity RMW outputs, optionally + install).
+#define CEC_EXACT_WRITES(X, N) X(N, 1, kAccNone) X(N, 2, kAccNone) X(N, 3, kAccNone) X(N, 4, kAccNone)
+#define CEC_EXACT_SHAPES(X)                                                                      \
+    CEC_EXACT_WRITES(X, 1) CEC_EXACT_WRITES(X, 2) CEC_EXACT_WRITES(X, 3) CEC_EXACT_WRITES(X, 4)  \
+    CEC_EXACT_WRITES(X, 5) CEC_EXACT_WRITES(X, 6) CEC_EXACT_WRITES(X, 7) CEC_EXACT_WRITES(X, 8)  \
+    X(1, 1, kAccAll) X(2, 1, kAccAll) X(2, 2, kAccAll) X(2, 3, kAccAll) X(2, 4, kAccAll)         \
+    X(2, 2, kAccAllButLast) X(2, 3, kAccAllButLast) X(2, 4, kAccAllButLast)
+
 template <class Eng>
 static bool launch_exact(int n, int l, int acc, const CombineArgs &a, int grid, size_t lds,
                          hipStream_t s) {
@@ -203,39 +211,44 @@ static bool launch_exact(int n, int l, int acc, const CombineArgs &a, int grid, 
         launch_k<N, L, Eng, A, true>(a, grid, lds, s);       \
         return true;                                             \
     }
-#define CEC_XL(N) CEC_X(N, 1, kAccNone) CEC_X(N, 2, kAccNone) CEC_X(N, 3, kAccNone) CEC_X(N, 4, kAccNone)
-    CEC_XL(1) CEC_XL(2) CEC_XL(3) CEC_XL(4) CEC_XL(5) CEC_XL(6) CEC_XL(7) CEC_XL(8)
-    CEC_X(1, 1, kAccAll) CEC_X(2, 1, kAccAll) CEC_X(2, 2, kAccAll) CEC_X(2, 3, kAccAll)
-    CEC_X(2, 4, kAccAll) CEC_X(2, 2, kAccAllButLast) CEC_X(2, 3, kAccAllButLast)
-    CEC_X(2, 4, kAccAllButLast)
-#undef CEC_XL
+    CEC_EXACT_SHAPES(CEC_X)
 #undef CEC_X
     return false;
 }
 
-// The (n_in, n_out, acc) shapes launch_exact instantiates.
 static bool has_exact(int n, int l, int acc) {
-    if (acc == kAccNone) return n >= 1 && n <= 8 && l >= 1 && l <= 4;
-    if (acc == kAccAll) return (n == 1 && l == 1) || (n == 2 && l >= 1 && l <= 4);
-    if (acc == kAccAllButLast) return n == 2 && l >= 2 && l <= 4;
+#define CEC_X(N, L, A) if (n == N && l == L && acc == A) return true;
+    CEC_EXACT_SHAPES(CEC_X)
+#undef CEC_X
     return false;
 }
 
-// Capacity kernels for every other shape (guarded, per-pattern counts and modes).
-// Returns the capacities instantiated (the launch record's nt / lt).
+// The capacity ladder: a launch of nt inputs and lt outputs that has no exact kernel runs
+// the capacity kernel of the next rung up, inputs 2 / 4 / 8 / 16 (the scrub kernels start
+// at 4) and outputs 1 / 2 / 4.  CEC_CAPACITY_RUNGS(nt, lt, K) runs K(NT, LT) for that rung;
+// K launches its kernel template and returns the Capacity (the launch record's nt / lt).
 struct Capacity {
     int nt, lt;
 };
+#define CEC_LT_RUNGS(lt, NT, K)                  \
+    if (lt <= 1) { K(NT, 1) }                    \
+    else if (lt <= 2) { K(NT, 2) }               \
+    else { K(NT, 4) }
+#define CEC_CAPACITY_RUNGS_FROM_4(nt, lt, K)     \
+    if (nt <= 4) { CEC_LT_RUNGS(lt, 4, K) }      \
+    else if (nt <= 8) { CEC_LT_RUNGS(lt, 8, K) } \
+    else { CEC_LT_RUNGS(lt, 16, K) }
+#define CEC_CAPACITY_RUNGS(nt, lt, K)            \
+    if (nt <= 2) { CEC_LT_RUNGS(lt, 2, K) }      \
+    else { CEC_CAPACITY_RUNGS_FROM_4(nt, lt, K) }
+
+// Capacity kernels for every shape without an exact one (guarded, per-pattern counts and modes).
 template <class Eng>
 static Capacity launch_generic(int nt, int lt, const CombineArgs &a, int grid, size_t lds, hipStream_t s) {
-#define CEC_G(NT)                                                                        \
-    if (lt <= 1) { launch_k<NT, 1, Eng, kAccRuntime, false>(a, grid, lds, s); return {NT, 1}; }       \
-    else if (lt <= 2) { launch_k<NT, 2, Eng, kAccRuntime, false>(a, grid, lds, s); return {NT, 2}; }  \
-    else { launch_k<NT, 4, Eng, kAccRuntime, false>(a, grid, lds, s); return {NT, 4}; }
-    if (nt <= 2) { CEC_G(2) }
-    else if (nt <= 4) { CEC_G(4) }
-    else if (nt <= 8) { CEC_G(8) }
-    else { CEC_G(16) }
+#define CEC_G(NT, LT)                                              \
+    launch_k<NT, LT, Eng, kAccRuntime, false>(a, grid, lds, s);   \
+    return {NT, LT};
+    CEC_CAPACITY_RUNGS(nt, lt, CEC_G)
 #undef CEC_G
 }
 
@@ -271,13 +284,6 @@ struct Streams {
     uint8_t *base[kMaxStreams] = {};
 };
 
-// One launch over a tile source (plan or implicit region) with a pattern set built for
-// `engine` (the patterns' coefficient form and the kernel must agree: the engine is read
-// once per op, so a concurrent cec_set_engine cannot split them).
-static int run_combine(int dev, const Streams &st, const std::vector<Pattern> &pats,
-                       const std::vector<uint8_t> &rows, const cec_plan *plan,
-                       uint64_t implicit_len, hipStream_t stream, const std::vector<char> *used, int engine);
-
 // ============================================================== plans
 // Tiles of one extent end on 4 KiB boundaries of the arena offset, so interior
 // tiles cover whole 128-B lines and only an extent's first / last tile shares a line
@@ -312,8 +318,7 @@ struct cec_plan {
     uint64_t total = 0;
     bool overlap = false;
     int64_t n_line_tiles = 0;   // full kTile tiles at a 128-B aligned arena offset
-    Tile *d_tiles = nullptr;    // from dev_cache() (owned plans only; views borrow)
-    bool owned = false;
+    Tile *d_tiles = nullptr;    // from dev_cache() (NULL: the empty plan)
     uint32_t max_pattern = 0;       // largest extent pattern (per-op index validation)
     std::vector<Tile> h_tiles;      // kept alive for the async upload
     mutable Tracker uses;           // the streams of the tile upload and of every launch
@@ -325,7 +330,7 @@ CEC_API int cec_plan_destroy(cec_plan *p) {
     // only this plan's own work: its upload and its launches on every stream used
     if (hipError_t e = p->uses.wait(p->device); e != hipSuccess)
         rc = fail(CEC_EHIP, "cec_plan_destroy: a launch of this plan failed: %s", hipGetErrorString(e));
-    if (p->owned) dev_cache().release(p->device, p->d_tiles, sizeof(Tile) * p->n_tiles);
+    dev_cache().release(p->device, p->d_tiles, sizeof(Tile) * p->n_tiles);  // (NULL: nothing)
     delete p;
     return rc;
 }
@@ -381,7 +386,6 @@ CEC_API int cec_plan_create(cec_plan **out, const cec_extent *ext, int n, void *
             delete p;
             return fail(CEC_ENOMEM, "cec_plan_create: %zu bytes of tiles", bytes);
         }
-        p->owned = true;
         if (hipMemcpyAsync(p->d_tiles, p->h_tiles.data(), bytes, hipMemcpyHostToDevice, s) != hipSuccess) {
             (void)hipGetLastError();
             cec_plan_destroy(p);
@@ -397,12 +401,47 @@ CEC_API int cec_plan_num_extents(const cec_plan *p) { return p ? p->n_ext : 0; }
 CEC_API int64_t cec_plan_num_tiles(const cec_plan *p) { return p ? p->n_tiles : 0; }
 CEC_API uint64_t cec_plan_total_bytes(const cec_plan *p) { return p ? p->total : 0; }
 
+// What one launch walks: a run of device tiles, or (tiles == NULL) the implicit 4 KiB
+// tiling of a region.  Made in one of the three ways below and no other, so the tile
+// count and the full-line-tile count -- which alone decides the workgroup split,
+// split_shift_for -- always come with the tiles.
+struct TileSource {
+    const Tile *tiles = nullptr;  // device address; NULL: the region [0, implicit_len)
+    uint64_t n_tiles = 0;
+    uint64_t n_line_tiles = 0;    // full kTile tiles at a 128-B aligned offset
+    uint64_t implicit_len = 0;
+    Tracker *uses = nullptr;      // a plan's streams, for its destroy; NULL for windows and
+                                  // regions, whose owners track their own calls
+
+    // A plan's tiles, on the device the plan was built on.
+    static int of_plan(const cec_plan *plan, int dev, TileSource *out) {
+        if (plan->device != dev)
+            return fail(CEC_EINVAL, "plan built on device %d used on device %d", plan->device, dev);
+        *out = {plan->d_tiles, static_cast<uint64_t>(plan->n_tiles), static_cast<uint64_t>(plan->n_line_tiles), 0,
+                &plan->uses};
+        return CEC_OK;
+    }
+    // The region [0, len): every tile counts as a full line tile (at most the last is short).
+    static int of_region(uint64_t len, TileSource *out) {
+        const uint64_t n = (len + kTile - 1) / kTile;
+        if (n > 0xFFFFFFFFull) return fail(CEC_EINVAL, "region too large");
+        *out = {nullptr, n, n, len, nullptr};
+        return CEC_OK;
+    }
+    // n tiles of an op's own tile buffer: d on the device, h the same tiles on the host.
+    static TileSource window(const Tile *d, const Tile *h, size_t n) {
+        return {d, n, static_cast<uint64_t>(count_line_tiles(h, n)), 0, nullptr};
+    }
+    // ... whose tiles the caller knows to be whole 4 KiB units at 4 KiB offsets.
+    static TileSource whole_units(const Tile *d, size_t n) { return {d, n, n, 0, nullptr}; }
+};
+
 // Workgroups per tile (log2).  Full tiles on 128-B lines stream fastest as four
-// 64-lane workgroups (finer dispatch, every wave equal work).  A plan that is mostly
+// 64-lane workgroups (finer dispatch, every wave equal work).  A launch that is mostly
 // small or line-misaligned tiles keeps one 256-lane workgroup per tile: splitting
 // those multiplies empty workgroups and partial lines written by two workgroups
 // (measured: DESIGN.md section 4).  CEC_SPLIT_SHIFT=0..2 pins the choice.
-static uint32_t split_shift_for(const Streams &st, const cec_plan *plan) {
+static uint32_t split_shift_for(const Streams &st, const TileSource &src) {
     static const int forced = [] {
         const char *e = getenv("CEC_SPLIT_SHIFT");
         return e && *e ? std::min(2, std::max(0, atoi(e))) : -1;
@@ -410,7 +449,7 @@ static uint32_t split_shift_for(const Streams &st, const cec_plan *plan) {
     if (forced >= 0) return static_cast<uint32_t>(forced);
     uintptr_t mis = 0;
     for (int i = 0; i < kMaxStreams; ++i) mis |= reinterpret_cast<uintptr_t>(st.base[i]);
-    const bool full = plan ? plan->n_line_tiles * 4 >= plan->n_tiles * 3 : true;
+    const bool full = src.n_line_tiles * 4 >= src.n_tiles * 3;
     return full && (mis & (kLineBytes - 1)) == 0 ? 2u : 0u;
 }
 
@@ -505,13 +544,6 @@ static LaunchShape launch_shape(const std::vector<Pattern> &pats, const std::vec
     return sh;
 }
 
-// One launch over n_tiles (> 0) tiles of a plan or an implicit region, with the tables
-// (n_pats patterns, then the LDS engine's rows) already on the device.  The caller
-// checks hipGetLastError.
-// *released: whether every wave of the launch ends with a system-scope release
-// (kFlagSysRelease asked for, and honoured: only the narrow 1 x 1 launches carry it).
-// hpats / used: the host copies of the launch's patterns and which of them its tiles
-// name (NULL: all), for the stream check below.
 enum KernelKind { kKindNarrow, kKindExact, kKindGeneric };
 static_assert(kKindNarrow == CEC_KERNEL_NARROW && kKindExact == CEC_KERNEL_EXACT &&
                   kKindGeneric == CEC_KERNEL_GENERIC, "cec_launch_record::kind");
@@ -520,22 +552,72 @@ static_assert(kAccNone == CEC_ACC_NONE && kAccAll == CEC_ACC_ALL && kAccAllButLa
 static_assert(kFlagSysRelease == CEC_LAUNCH_SYS_RELEASE && kFlagWriteThrough == CEC_LAUNCH_WRITE_THROUGH,
               "cec_launch_record::flags");
 
-// The calling thread's last enqueued kernel launch (cec_last_launch), filled by
-// launch_combine: every launch of the library goes through it.
+// The calling thread's last enqueued kernel launch (cec_last_launch).  record_launch is
+// the one place that writes it: launch_combine and scrub_launch, the library's two
+// launch routines, each call it once per kernel they enqueue.
 static thread_local cec_launch_record t_last_launch = {0, -1, 0, 0, -1, -1, 0, 0, 0, 0, 0};
 
-// Launch-time check of the argument block a kernel of `kind` is passed: every stream
-// slot a used pattern names must be one the block carries (below 2 for the narrow
-// kernels, whose block is narrow_args' copy of the first two slots; below kMaxStreams
-// otherwise) and hold a non-NULL base there.  Which arena the op meant for each slot is
-// decided by the op itself (it fills the slots); this check catches a kernel choice or
-// an argument block that cannot serve the patterns -- a slot the kernel's block does not
-// have, or an empty one -- which would otherwise fault the GPU.  A failure is refused.
-static bool stream_layout_ok(const uint8_t *const *bases, int slots, const Pattern *hpats, size_t n_pats,
-                             const std::vector<char> *used) {
-    for (size_t q = 0; q < n_pats; ++q) {
-        if (used && (q >= used->size() || !(*used)[q])) continue;
-        const Pattern &p = hpats[q];
+static void record_launch(int kind, Capacity cap, int acc, bool lds, uint32_t split_shift, uint32_t flags,
+                          uint32_t grid, uint64_t n_tiles, size_t lds_bytes) {
+    t_last_launch = {t_last_launch.seq + 1, kind, cap.nt, cap.lt, acc, lds ? CEC_ENGINE_LDS : CEC_ENGINE_PERM,
+                     split_shift, flags, grid, n_tiles, lds_bytes};
+}
+
+CEC_API int cec_last_launch(cec_launch_record *out) {
+    if (!out) return fail(CEC_EINVAL, "cec_last_launch: out is NULL");
+    *out = t_last_launch;
+    return CEC_OK;
+}
+
+// Test hook (cec_internal_fail_launch): the calling thread's next `after` launches run, the
+// one after them is refused as a HIP failure, then the hook disarms.  -1: off.
+// Counted by run_combine and scrub_launch (launch_countdown), before anything is built.
+static thread_local int t_fail_after = -1;
+CEC_API int cec_internal_fail_launch(int after) {
+    t_fail_after = after < 0 ? -1 : after;
+    return CEC_OK;
+}
+static int launch_countdown() {
+    if (t_fail_after == 0) {
+        t_fail_after = -1;
+        return fail(CEC_EHIP, "injected launch failure (cec_internal_fail_launch)");
+    }
+    if (t_fail_after > 0) --t_fail_after;
+    return CEC_OK;
+}
+
+// The device copy of a pattern set from the coefficient cache, for a launch on stream s:
+// patterns and the LDS engine's product rows are one blob, rows after the patterns (16-B
+// aligned: sizeof(Pattern) is a multiple of 16), and the blob's bytes are its cache key.
+// *entry is pinned against eviction until pattern_done, which the caller calls once its
+// launch is enqueued (eviction synchronises the device).
+static int pattern_tables(int dev, const std::vector<Pattern> &pats, const std::vector<uint8_t> &rows,
+                          hipStream_t s, PatEntry **entry) {
+    std::string key(reinterpret_cast<const char *>(pats.data()), pats.size() * sizeof(Pattern));
+    key.append(reinterpret_cast<const char *>(rows.data()), rows.size());
+    return pattern_get(dev, std::move(key), s, entry);
+}
+
+// The pattern set of one launch: where it lies on the device, and its host copy for the
+// launch-time stream check.
+struct Tables {
+    const uint8_t *d;               // device blob: n_pats patterns, then the LDS engine's rows
+    size_t n_pats;
+    const Pattern *host;            // the same patterns on the host
+    const std::vector<char> *used;  // which of them the launch's tiles name (NULL: all)
+};
+
+// Launch-time check of the argument block a kernel is passed: every stream slot a used
+// pattern names must be one the block carries (below 2 for the narrow kernels, whose
+// block is narrow_args' copy of the first two slots; below kMaxStreams otherwise) and
+// hold a non-NULL base there.  Which arena the op meant for each slot is decided by the
+// op itself (it fills the slots); this check catches a kernel choice or an argument block
+// that cannot serve the patterns -- a slot the kernel's block does not have, or an empty
+// one -- which would otherwise fault the GPU.  A failure is refused.
+static bool stream_layout_ok(const uint8_t *const *bases, int slots, const Tables &tb) {
+    for (size_t q = 0; q < tb.n_pats; ++q) {
+        if (tb.used && (q >= tb.used->size() || !(*tb.used)[q])) continue;
+        const Pattern &p = tb.host[q];
         for (int i = 0; i < p.n_in; ++i)
             if (p.in_stream[i] >= slots || !bases[p.in_stream[i]]) return false;
         for (int l = 0; l < p.n_out; ++l)
@@ -544,22 +626,20 @@ static bool stream_layout_ok(const uint8_t *const *bases, int slots, const Patte
     return true;
 }
 
-static bool layout_ok_for(KernelKind kind, const CombineArgs &a, const Pattern *hpats, size_t n_pats,
-                          const std::vector<char> *used) {
-    if (kind == kKindNarrow) {
-        const CombineArgsN<kNarrowStreams> na = narrow_args(a);
-        return stream_layout_ok(na.base, kNarrowStreams, hpats, n_pats, used);
-    }
-    return stream_layout_ok(a.base, kMaxStreams, hpats, n_pats, used);
+// `narrow`: the block a narrow kernel is passed (NULL: the launch passes `a` itself).
+static bool layout_ok_for(const CombineArgs &a, const CombineArgsN<kNarrowStreams> *narrow, const Tables &tb) {
+    return narrow ? stream_layout_ok(narrow->base, kNarrowStreams, tb) : stream_layout_ok(a.base, kMaxStreams, tb);
 }
 
-static int launch_combine(int dev, const Streams &st, const uint8_t *tables, size_t n_pats,
-                          const LaunchShape &sh, bool lds, const cec_plan *plan, uint64_t implicit_len,
-                          uint64_t n_tiles, hipStream_t stream, const Pattern *hpats,
-                          const std::vector<char> *used, uint32_t flags = 0, bool *released = nullptr) {
+// One launch over the tiles of `src` (at least one) with the tables `tb` already on the
+// device, recorded for cec_last_launch.  The caller checks hipGetLastError.
+// *released: whether every wave of the launch ends with a system-scope release
+// (kFlagSysRelease asked for, and honoured: only the narrow 1 x 1 launches carry it).
+static int launch_combine(int dev, const Streams &st, const Tables &tb, const LaunchShape &sh, bool lds,
+                          const TileSource &src, hipStream_t stream, uint32_t flags = 0, bool *released = nullptr) {
     CombineArgs a;
     memset(&a, 0, sizeof a);
-    a.flags = flags | (write_through(n_tiles, sh.nt + sh.lt) ? kFlagWriteThrough : 0u);
+    a.flags = flags | (write_through(src.n_tiles, sh.nt + sh.lt) ? kFlagWriteThrough : 0u);
     // Which kernel runs: the exact-shape one if the shape has an instantiation, the narrow
     // two-slot one for 1 x 1 launches over slots 0 and 1, else a capacity kernel.
     const bool exact_k = sh.exact && has_exact(sh.en, sh.el, sh.eacc);
@@ -569,30 +649,31 @@ static int launch_combine(int dev, const Streams &st, const uint8_t *tables, siz
             ? kKindNarrow
             : exact_k ? kKindExact : kKindGeneric;
     for (int i = 0; i < kMaxStreams; ++i) a.base[i] = st.base[i];
-    if (!layout_ok_for(kind, a, hpats, n_pats, used))
-        return fail(CEC_EINVAL, "internal: a launch's argument block cannot serve its patterns "
-                                "(kind %d, %d x %d); not launched", static_cast<int>(kind), sh.en, sh.el);
-    if (plan) a.tiles = plan->d_tiles;
-    else a.implicit_len = implicit_len;
-    a.patterns = reinterpret_cast<const Pattern *>(tables);
-    a.rows = tables + n_pats * sizeof(Pattern);
-    a.n_tiles = static_cast<uint32_t>(n_tiles);
+    a.tiles = src.tiles;
+    a.implicit_len = src.implicit_len;
+    a.patterns = reinterpret_cast<const Pattern *>(tb.d);
+    a.rows = tb.d + tb.n_pats * sizeof(Pattern);
+    a.n_tiles = static_cast<uint32_t>(src.n_tiles);
     // One workgroup per (part of a) tile, dispatched in tile order, so the set of
     // tiles in flight is a contiguous window of the arenas (measured 5-12 % over a
     // persistent grid-stride grid: DESIGN.md).  The LDS engine stages its pattern's
     // product rows per workgroup (512 B for an RS(3,2) encode, from L2).
-    a.split_shift = split_shift_for(st, plan);
+    a.split_shift = split_shift_for(st, src);
     const size_t lds_bytes = std::max(lds ? static_cast<size_t>(sh.max_rows) * 256 : 0,
                                       occupancy_lds(dev, a.split_shift));
     // A dispatch holds at most 2^32 - 1 work items per dimension: past that (more than
     // 64 GiB of tiles per stream) workgroups walk the rest grid-stride.
     const uint64_t max_wgs = 0xFFFFFFFFull / (kBlock >> a.split_shift);
-    const int grid = static_cast<int>(std::min<uint64_t>(n_tiles << a.split_shift, max_wgs));
+    const int grid = static_cast<int>(std::min<uint64_t>(src.n_tiles << a.split_shift, max_wgs));
     a.grid = static_cast<uint32_t>(grid);
+    CombineArgsN<kNarrowStreams> na;  // the narrow kernels' block: checked and passed
+    if (kind == kKindNarrow) na = narrow_args(a);
+    if (!layout_ok_for(a, kind == kKindNarrow ? &na : nullptr, tb))
+        return fail(CEC_EINVAL, "internal: a launch's argument block cannot serve its patterns "
+                                "(kind %d, %d x %d); not launched", static_cast<int>(kind), sh.en, sh.el);
     bool ok;
     Capacity cap = {sh.en, sh.el};  // exact and narrow kernels: the shape itself
     if (kind == kKindNarrow) {
-        const CombineArgsN<kNarrowStreams> na = narrow_args(a);
         ok = lds ? launch_narrow<LdsEngine>(sh.eacc, na, grid, lds_bytes, stream)
                  : launch_narrow<PermEngine>(sh.eacc, na, grid, lds_bytes, stream);
     } else if (kind == kKindExact) {
@@ -606,66 +687,26 @@ static int launch_combine(int dev, const Streams &st, const uint8_t *tables, siz
     if (!ok) return fail(CEC_EINVAL, "internal: no %s kernel for %d x %d", kind == kKindNarrow ? "narrow" : "exact",
                          sh.en, sh.el);
     if (released) *released = kind == kKindNarrow && (flags & kFlagSysRelease) != 0;
-    cec_launch_record &rec = t_last_launch;
-    rec.seq += 1;
-    rec.kind = kind;
-    rec.nt = cap.nt;
-    rec.lt = cap.lt;
-    rec.acc = kind == kKindGeneric ? static_cast<int>(kAccRuntime) : sh.eacc;
-    rec.engine = lds ? CEC_ENGINE_LDS : CEC_ENGINE_PERM;
-    rec.split_shift = a.split_shift;
-    rec.flags = a.flags;
-    rec.grid = a.grid;
-    rec.n_tiles = n_tiles;
-    rec.lds_bytes = lds_bytes;
+    record_launch(kind, cap, kind == kKindGeneric ? static_cast<int>(kAccRuntime) : sh.eacc, lds, a.split_shift,
+                  a.flags, a.grid, src.n_tiles, lds_bytes);
     return CEC_OK;
 }
 
-CEC_API int cec_last_launch(cec_launch_record *out) {
-    if (!out) return fail(CEC_EINVAL, "cec_last_launch: out is NULL");
-    *out = t_last_launch;
-    return CEC_OK;
-}
-
-// Test hook (cec_internal_fail_launch): the calling thread's next `after` launches run, the
-// one after them is refused as a HIP failure, then the hook disarms.  -1: off.
-static thread_local int t_fail_after = -1;
-CEC_API int cec_internal_fail_launch(int after) {
-    t_fail_after = after < 0 ? -1 : after;
-    return CEC_OK;
-}
-
+// One launch over a tile source with a pattern set built for `engine` (the patterns'
+// coefficient form and the kernel must agree: the engine is read once per op, so a
+// concurrent cec_set_engine cannot split them).
 static int run_combine(int dev, const Streams &st, const std::vector<Pattern> &pats,
-                       const std::vector<uint8_t> &rows, const cec_plan *plan,
-                       uint64_t implicit_len, hipStream_t stream, const std::vector<char> *used, int engine) {
-    if (t_fail_after == 0) {
-        t_fail_after = -1;
-        return fail(CEC_EHIP, "injected launch failure (cec_internal_fail_launch)");
-    }
-    if (t_fail_after > 0) --t_fail_after;
-    uint64_t n_tiles;
-    if (plan) {
-        if (plan->device != dev)
-            return fail(CEC_EINVAL, "plan built on device %d used on device %d", plan->device, dev);
-        n_tiles = static_cast<uint64_t>(plan->n_tiles);
-    } else {
-        n_tiles = (implicit_len + kTile - 1) / kTile;
-        if (n_tiles > 0xFFFFFFFFull) return fail(CEC_EINVAL, "region too large");
-    }
-    if (n_tiles == 0 || pats.empty()) return CEC_OK;
+                       const std::vector<uint8_t> &rows, const TileSource &src, hipStream_t stream,
+                       const std::vector<char> *used, int engine) {
+    if (int r = launch_countdown()) return r;
+    if (src.n_tiles == 0 || pats.empty()) return CEC_OK;
     const LaunchShape sh = launch_shape(pats, used);
     if (sh.lt == 0) return CEC_OK;
-    // Patterns and the LDS engine's product rows are uploaded as one blob: rows follow
-    // the patterns (16-B aligned: sizeof(Pattern) is a multiple of 16).
-    std::string key(reinterpret_cast<const char *>(pats.data()), pats.size() * sizeof(Pattern));
-    key.append(reinterpret_cast<const char *>(rows.data()), rows.size());
     PatEntry *entry = nullptr;
-    if (int r = pattern_get(dev, std::move(key), stream, &entry)) return r;
-    const int rc = launch_combine(dev, st, entry->d, pats.size(), sh, engine == CEC_ENGINE_LDS, plan,
-                                  implicit_len, n_tiles, stream, pats.data(), used);
-    // the plan's streams, for its destroy (host-side only); the tables may be evicted
-    // again once the launch is enqueued (eviction synchronises the device)
-    if (plan) plan->uses.note(stream);
+    if (int r = pattern_tables(dev, pats, rows, stream, &entry)) return r;
+    const int rc = launch_combine(dev, st, Tables{entry->d, pats.size(), pats.data(), used}, sh,
+                                  engine == CEC_ENGINE_LDS, src, stream);
+    if (src.uses) src.uses->note(stream);  // a plan's streams, for its destroy (host-side only)
     pattern_done(entry);
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
@@ -729,9 +770,8 @@ static int build_patterns(const std::vector<Combo> &combos, size_t g, int engine
 // `used`: which combos the launch's tiles name (NULL = all; a persistent pattern table
 // may hold more than one launch uses: the kernel shape is chosen from the used ones).
 // `lds_op`: the op AUTO runs with the LDS engine (op_engine).
-static int run_combos(int dev, const Streams &st, const std::vector<Combo> &combos,
-                      const cec_plan *plan, uint64_t implicit_len, hipStream_t stream,
-                      const std::vector<char> *used = nullptr, bool lds_op = false) {
+static int run_combos(int dev, const Streams &st, const std::vector<Combo> &combos, const TileSource &src,
+                      hipStream_t stream, const std::vector<char> *used = nullptr, bool lds_op = false) {
     size_t max_out = 0;
     for (const Combo &c : combos) max_out = std::max(max_out, c.outs.size());
     const int engine = op_engine(lds_op);
@@ -740,9 +780,22 @@ static int run_combos(int dev, const Streams &st, const std::vector<Combo> &comb
         std::vector<Pattern> pats;
         std::vector<uint8_t> rows;
         if (int r = build_patterns(combos, g, engine, pats, rows)) return r;
-        if (int r = run_combine(dev, st, pats, rows, plan, implicit_len, stream, used, engine)) return r;
+        if (int r = run_combine(dev, st, pats, rows, src, stream, used, engine)) return r;
     }
     return CEC_OK;
+}
+// The ops' two forms: over the tiles of a plan, and over the region [0, len).
+static int run_combos_plan(int dev, const Streams &st, const std::vector<Combo> &combos, const cec_plan *plan,
+                           hipStream_t stream, bool lds_op = false) {
+    TileSource src;
+    if (int r = TileSource::of_plan(plan, dev, &src)) return r;
+    return run_combos(dev, st, combos, src, stream, nullptr, lds_op);
+}
+static int run_combos_region(int dev, const Streams &st, const std::vector<Combo> &combos, uint64_t len,
+                             hipStream_t stream) {
+    TileSource src;
+    if (int r = TileSource::of_region(len, &src)) return r;
+    return run_combos(dev, st, combos, src, stream);
 }
 
 static int check_code(int k, int m, const int *matrix) {
@@ -823,7 +876,8 @@ CEC_API int cec_internal_check_launch_layout(int narrow, const int *in_slots, in
     CombineArgs a;
     memset(&a, 0, sizeof a);
     for (int i = 0; i < n_bases; ++i) a.base[i] = static_cast<uint8_t *>(const_cast<void *>(bases[i]));
-    if (!layout_ok_for(narrow ? kKindNarrow : kKindExact, a, &p, 1, nullptr))
+    const CombineArgsN<kNarrowStreams> na = narrow_args(a);
+    if (!layout_ok_for(a, narrow ? &na : nullptr, Tables{nullptr, 1, &p, nullptr}))
         return fail(CEC_EINVAL, "internal: a launch's argument block cannot serve its patterns; not launched");
     return CEC_OK;
 }
@@ -841,7 +895,8 @@ CEC_API int cec_get_waves_per_cu(void) { return waves_per_cu_cap(); }
 // the lookup (tools/dropin_breakdown.hip: 3.4 us of host time per call against 0.9 us
 // for an empty launch).  The memo is used only once the tables' upload is known
 // complete (until then the cache orders each launch after it), and never while
-// capturing (the cache then marks the tables).
+// capturing (the cache then marks the tables: a launch inside a capture fills a
+// RegionMemo of its own on the stack, which unpins them when the call returns).
 namespace {
 struct RegionMemo {
     int dev = -1, key = -1;
@@ -859,16 +914,17 @@ thread_local RegionMemo t_region;
 // flags / *released: see launch_combine (the 1 x 1 region launches honour the release).
 static int region_launch(int dev, const void *src, int multby, size_t n, void *dst, int add, hipStream_t s,
                          bool plain, uint32_t flags = 0, bool *released = nullptr) {
-    const uint64_t n_tiles = (n + kTile - 1) / kTile;
-    if (n_tiles > 0xFFFFFFFFull) return fail(CEC_EINVAL, "region too large");
+    TileSource region;
+    if (int r = TileSource::of_region(n, &region)) return r;
     const int engine = op_engine(false);
     const int key = (engine << 9) | (add ? 256 : 0) | multby;
     const bool capturing = !plain && stream_capturing(s);
-    RegionMemo &m = t_region;
     Streams st;
     st.base[0] = static_cast<uint8_t *>(const_cast<void *>(src));
     st.base[1] = static_cast<uint8_t *>(dst);
-    if (!(m.e && m.dev == dev && m.key == key && !capturing && m.e->up_done.load(std::memory_order_acquire))) {
+    RegionMemo once;            // while capturing: tables pinned for this launch only
+    RegionMemo *m = &t_region;  // the tables this launch runs with
+    if (!(m->e && m->dev == dev && m->key == key && !capturing && m->e->up_done.load(std::memory_order_acquire))) {
         Combo cb;
         cb.n_in = 1;
         cb.in_stream[0] = 0;
@@ -880,27 +936,18 @@ static int region_launch(int dev, const void *src, int multby, size_t n, void *d
         std::vector<Pattern> pats;
         std::vector<uint8_t> rows;
         if (int r = build_patterns({cb}, 0, engine, pats, rows, true)) return r;
-        std::string k(reinterpret_cast<const char *>(pats.data()), pats.size() * sizeof(Pattern));
-        k.append(reinterpret_cast<const char *>(rows.data()), rows.size());
         PatEntry *e = nullptr;
-        if (int r = pattern_get(dev, std::move(k), s, &e)) return r;
-        if (capturing) {  // tables now marked captured: pinned for this launch only
-            const int rc = launch_combine(dev, st, e->d, 1, launch_shape(pats, nullptr), engine == CEC_ENGINE_LDS,
-                                          nullptr, n, n_tiles, s, pats.data(), nullptr, flags, released);
-            pattern_done(e);
-            if (rc) return rc;
-            HIP_TRY(hipGetLastError());
-            return CEC_OK;
-        }
-        if (m.e) pattern_done(m.e);  // this launch's pin becomes the memo's
-        m.dev = dev;
-        m.key = key;
-        m.e = e;
-        m.shape = launch_shape(pats, nullptr);
-        m.pat = pats[0];
+        if (int r = pattern_tables(dev, pats, rows, s, &e)) return r;
+        if (capturing) m = &once;           // (the cache marked the tables captured)
+        else if (m->e) pattern_done(m->e);  // this launch's pin becomes the memo's
+        m->dev = dev;
+        m->key = key;
+        m->e = e;
+        m->shape = launch_shape(pats, nullptr);
+        m->pat = pats[0];
     }
-    if (int rc = launch_combine(dev, st, m.e->d, 1, m.shape, engine == CEC_ENGINE_LDS, nullptr, n, n_tiles, s,
-                                &m.pat, nullptr, flags, released))
+    if (int rc = launch_combine(dev, st, Tables{m->e->d, 1, &m->pat, nullptr}, m->shape, engine == CEC_ENGINE_LDS,
+                                region, s, flags, released))
         return rc;
     HIP_TRY(hipGetLastError());
     return CEC_OK;
@@ -954,7 +1001,8 @@ static int encode_common(int k, int m, const int *matrix, const uint8_t *const *
         for (int j = 0; j < k; ++j) o.coef[j] = MATRIX(k + p, j);
         c.outs.push_back(o);
     }
-    return run_combos(dev, st, {c}, plan, len, static_cast<hipStream_t>(stream));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return plan ? run_combos_plan(dev, st, {c}, plan, s) : run_combos_region(dev, st, {c}, len, s);
 }
 
 // Ops with one pattern index every tile's pattern field into a one-entry table: it must be 0.
@@ -1019,7 +1067,7 @@ CEC_API int cec_diff_update(int k, int m, const int *matrix, uint8_t *const *dat
     }
     // AUTO: PERM.  The LDS engine's diff-update was within +-3 % of PERM either way over
     // the recorded boxes (median margin under 1 %; DESIGN.md §4 "Engine per op").
-    return run_combos(dev, st, combos, plan, 0, static_cast<hipStream_t>(stream));
+    return run_combos_plan(dev, st, combos, plan, static_cast<hipStream_t>(stream));
 }
 
 CEC_API int cec_set_diff(int k, const uint8_t *const *data, const uint8_t *staging, uint8_t *diff,
@@ -1051,7 +1099,7 @@ CEC_API int cec_set_diff(int k, const uint8_t *const *data, const uint8_t *stagi
         o.coef[0] = o.coef[1] = 1;
         c.outs.push_back(o);
     }
-    return run_combos(dev, st, combos, plan, 0, static_cast<hipStream_t>(stream));
+    return run_combos_plan(dev, st, combos, plan, static_cast<hipStream_t>(stream));
 }
 
 CEC_API int cec_apply_diffs(int k, int m, const int *matrix, int lid_self, const uint8_t *diffs,
@@ -1079,7 +1127,7 @@ CEC_API int cec_apply_diffs(int k, int m, const int *matrix, int lid_self, const
         o.coef[0] = MATRIX(lid_self, j);
         c.outs.push_back(o);
     }
-    return run_combos(dev, st, combos, plan, 0, static_cast<hipStream_t>(stream));
+    return run_combos_plan(dev, st, combos, plan, static_cast<hipStream_t>(stream));
 }
 
 static int mask_ok(int k, int m, uint32_t mask) {
@@ -1119,7 +1167,7 @@ CEC_API int cec_residual(int k, int m, const int *matrix, int lid_self, uint32_t
     }
     st.base[k + m] = residual;
     c.outs.push_back(o);
-    return run_combos(dev, st, {c}, plan, 0, static_cast<hipStream_t>(stream));
+    return run_combos_plan(dev, st, {c}, plan, static_cast<hipStream_t>(stream));
 }
 
 // Lost data lids and participating parity lids of a recovery mask, ascending
@@ -1173,7 +1221,7 @@ CEC_API int cec_solve(int k, int m, const int *matrix, uint32_t mask,
         for (int r = 0; r < n; ++r) o.coef[r] = inv[x * n + r];  // memcached.c:7916-7922
         c.outs.push_back(o);
     }
-    return run_combos(dev, st, {c}, plan, 0, static_cast<hipStream_t>(stream));
+    return run_combos_plan(dev, st, {c}, plan, static_cast<hipStream_t>(stream));
 }
 
 CEC_API int cec_decode(int k, int m, const int *matrix, const uint32_t *masks, int n_masks,
@@ -1227,8 +1275,7 @@ CEC_API int cec_decode(int k, int m, const int *matrix, const uint32_t *masks, i
     // AUTO: values of 64 KiB and more (large_values) run the LDS engine, ahead of PERM by a
     // median 3 % there (rotating or one mask: configs[4]'s 1 MiB D1-by-P1 rebuild +4.9 %);
     // 4 KiB values run PERM (rotating masks -1.7 %, one mask +1.1 %: within 2 %)
-    return run_combos(dev, st, combos, plan, 0, static_cast<hipStream_t>(stream), nullptr,
-                      large_values(plan));
+    return run_combos_plan(dev, st, combos, plan, static_cast<hipStream_t>(stream), large_values(plan));
 }
 
 CEC_API uint32_t cec_recovery_mask(int k, int m, int leader_lid, const int *connected) {

@@ -1,5 +1,8 @@
 // cec_scrub.inc -- device parity check: locate and repair bad 4 KiB units.
-// Included by cec_runtime.hip (shares its launch internals); not a separate TU.
+// Included by cec_runtime.hip; not a separate TU.  scrub_launch is the library's second
+// launch routine beside launch_combine and is built from the same parts: a TileSource to
+// walk, pattern_tables for its coefficients, the launch_countdown hook, split_shift_for,
+// the capacity ladder and record_launch.  Only the kernel and its argument block differ.
 //
 // Where the server would call it: the idle loop (idle_event_handler,
 // memcached.c:5712-5734) walks the arenas in idle time, and after a CEC_EHIP from
@@ -26,20 +29,15 @@ void launch_scrub_k(const ScrubArgs &a, size_t lds, hipStream_t s) {
 }
 
 // The kernel of a launch over k data and lt parity streams: exact for the codes the suite
-// uses (only when the launch holds the code's every parity), else capacities.
-Capacity launch_scrub(int k, int lt, bool whole_code, const ScrubArgs &a, size_t lds, hipStream_t s, bool *exact) {
-    *exact = true;
+// uses (only when the launch holds the code's every parity), else the capacity ladder's.
+Capacity launch_scrub(int k, int lt, bool whole_code, const ScrubArgs &a, size_t lds, hipStream_t s) {
     if (whole_code && k == 3 && lt == 2) { launch_scrub_k<3, 2, true>(a, lds, s); return {3, 2}; }
     if (whole_code && k == 4 && lt == 2) { launch_scrub_k<4, 2, true>(a, lds, s); return {4, 2}; }
     if (whole_code && k == 6 && lt == 3) { launch_scrub_k<6, 3, true>(a, lds, s); return {6, 3}; }
-    *exact = false;
-#define CEC_SG(NT)                                                                 \
-    if (lt <= 1) { launch_scrub_k<NT, 1, false>(a, lds, s); return {NT, 1}; }      \
-    else if (lt <= 2) { launch_scrub_k<NT, 2, false>(a, lds, s); return {NT, 2}; } \
-    else { launch_scrub_k<NT, 4, false>(a, lds, s); return {NT, 4}; }
-    if (k <= 4) { CEC_SG(4) }
-    else if (k <= 8) { CEC_SG(8) }
-    else { CEC_SG(16) }
+#define CEC_SG(NT, LT)                          \
+    launch_scrub_k<NT, LT, false>(a, lds, s);  \
+    return {NT, LT};
+    CEC_CAPACITY_RUNGS_FROM_4(k, lt, CEC_SG)
 #undef CEC_SG
 }
 
@@ -110,13 +108,8 @@ CEC_API int cec_scrub_release_stream(cec_scrub_report *s, void *stream) {
 
 // One launch: parities [p0, p0 + lt) of the code against the k data streams.
 static int scrub_launch(int dev, cec_scrub_report *s, int k, int m, const int *matrix, const uint8_t *const *data,
-                        const uint8_t *const *parity, int p0, int lt, const cec_plan *plan, uint64_t len,
-                        uint64_t n_tiles, hipStream_t stream) {
-    if (t_fail_after == 0) {  // the fault hook of run_combine
-        t_fail_after = -1;
-        return fail(CEC_EHIP, "injected launch failure (cec_internal_fail_launch)");
-    }
-    if (t_fail_after > 0) --t_fail_after;
+                        const uint8_t *const *parity, int p0, int lt, const TileSource &src, hipStream_t stream) {
+    if (int rc = launch_countdown()) return rc;
     // [0]: the syndrome's coefficients; [1]: ratio[q][j] = MATRIX(k+p0+q, j) / MATRIX(k+p0, j)
     // as PERM tables (a zero denominator leaves the zero table: lid j is then ruled out
     // wherever S_q is non-zero, which errs towards UNLOCATED)
@@ -139,37 +132,24 @@ static int scrub_launch(int dev, cec_scrub_report *s, int k, int m, const int *m
     Streams st;  // (for split_shift_for: every base of the launch)
     for (int j = 0; j < k; ++j) a.base[j] = st.base[j] = const_cast<uint8_t *>(data[j]);
     for (int l = 0; l < lt; ++l) a.base[k + l] = st.base[k + l] = const_cast<uint8_t *>(parity[p0 + l]);
-    std::string key(reinterpret_cast<const char *>(pats.data()), pats.size() * sizeof(Pattern));
     PatEntry *entry = nullptr;
-    if (int rc = pattern_get(dev, std::move(key), stream, &entry)) return rc;
-    if (plan) a.tiles = plan->d_tiles;
-    else a.implicit_len = len;
+    if (int rc = pattern_tables(dev, pats, {}, stream, &entry)) return rc;
+    a.tiles = src.tiles;
+    a.implicit_len = src.implicit_len;
     a.pattern = reinterpret_cast<const Pattern *>(entry->d);
     a.words = s->d_buf + kScrubHead;
     a.counter = s->d_buf;
-    a.n_tiles = static_cast<uint32_t>(n_tiles);
-    a.split_shift = split_shift_for(st, plan);
-    a.grid = static_cast<uint32_t>(n_tiles << a.split_shift);  // (n_tiles <= kScrubMaxTiles: fits)
+    a.n_tiles = static_cast<uint32_t>(src.n_tiles);
+    a.split_shift = split_shift_for(st, src);
+    a.grid = static_cast<uint32_t>(src.n_tiles << a.split_shift);  // (n_tiles <= kScrubMaxTiles: fits)
     a.syn_shift = static_cast<uint32_t>(p0);
     const size_t lds_bytes = occupancy_lds(dev, a.split_shift);
-    bool exact = false;
-    const Capacity cap = launch_scrub(k, lt, p0 == 0 && lt == m, a, lds_bytes, stream, &exact);
-    if (plan) plan->uses.note(stream);
+    const Capacity cap = launch_scrub(k, lt, p0 == 0 && lt == m, a, lds_bytes, stream);
+    if (src.uses) src.uses->note(stream);
     s->uses.note(stream);
     pattern_done(entry);
     HIP_TRY(hipGetLastError());
-    cec_launch_record &rec = t_last_launch;
-    rec.seq += 1;
-    rec.kind = CEC_KERNEL_SCRUB;
-    rec.nt = cap.nt;
-    rec.lt = cap.lt;
-    rec.acc = kAccAll;
-    rec.engine = CEC_ENGINE_PERM;
-    rec.split_shift = a.split_shift;
-    rec.flags = 0;
-    rec.grid = a.grid;
-    rec.n_tiles = n_tiles;
-    rec.lds_bytes = lds_bytes;
+    record_launch(CEC_KERNEL_SCRUB, cap, kAccAll, false, a.split_shift, 0, a.grid, src.n_tiles, lds_bytes);
     return CEC_OK;
 }
 
@@ -189,8 +169,8 @@ static int scrub_common(cec_scrub_report *s, int k, int m, const int *matrix, co
     int dev;
     if (int r = current_device(&dev)) return r;
     if (s->device != dev) return fail(CEC_EINVAL, "report built on device %d used on device %d", s->device, dev);
-    if (plan && plan->device != dev)
-        return fail(CEC_EINVAL, "plan built on device %d used on device %d", plan->device, dev);
+    TileSource src;
+    if (int r = plan ? TileSource::of_plan(plan, dev, &src) : TileSource::of_region(len, &src)) return r;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     s->valid = s->waited = s->fetched = false;  // until this run is enqueued in full
     t_last_engine = CEC_ENGINE_PERM;            // whatever cec_set_engine says
@@ -198,8 +178,7 @@ static int scrub_common(cec_scrub_report *s, int k, int m, const int *matrix, co
     HIP_TRY(hipMemsetAsync(s->d_buf, 0, sizeof(uint32_t) * (kScrubHead + n_tiles), stream));
     if (n_tiles)
         for (int p0 = 0; p0 < m; p0 += kPatL)
-            if (int r = scrub_launch(dev, s, k, m, matrix, data, parity, p0, std::min<int>(kPatL, m - p0), plan,
-                                     len, n_tiles, stream))
+            if (int r = scrub_launch(dev, s, k, m, matrix, data, parity, p0, std::min<int>(kPatL, m - p0), src, stream))
                 return r;
     HIP_TRY(hipMemcpyAsync(s->h_buf, s->d_buf, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     s->stream = stream;
