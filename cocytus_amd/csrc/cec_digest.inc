@@ -1,0 +1,145 @@
+// cec_digest.inc -- 32-byte linear unit digests, and the scrub over them.
+// Included by cec_runtime.hip after cec_scrub.inc; not a separate TU.
+//
+// cec_scrub needs all k + m arenas of a group on one device; Cocytus runs one process per
+// shard.  The code is linear over GF(2^8), and so is the digest (cec_kernels.hpp), so
+// digest(parity_p) = sum_j MATRIX(k+p, j) * digest(data_j): each process digests its own
+// arena (cec_digest, 32 B per 4 KiB unit), ships the digests, and the leader runs the
+// scrub's syndrome and ratio test on them (cec_scrub_digests) into the same
+// cec_scrub_report -- wait / findings / classify / repair are cec_scrub.inc's, unchanged.
+// Built from the library's parts: a TileSource to walk, launch_countdown, scrub_patterns +
+// pattern_tables for the check's coefficients, the capacity ladder, record_launch.
+
+namespace {
+
+// One dispatch holds 2^32 - 1 work items; a digest launch has one wave per (tile, arena).
+constexpr uint64_t kDigestMaxWork = 0xFFFFFFFFull / kBlock * (kBlock / 64);
+
+// Waves (work items) per workgroup, log2.  Four: a 256-lane workgroup whose waves each
+// take their own (tile, arena).  One-wave workgroups, the combine kernels' split of full
+// tiles, measured 10-12 % slower here (327,680 workgroups of 4 KiB each against 81,920:
+// DESIGN.md section 8).  CEC_DIGEST_WAVES_SHIFT=0..2 pins another (measurement).
+uint32_t digest_waves_shift() {
+    static const uint32_t shift = [] {
+        const char *e = getenv("CEC_DIGEST_WAVES_SHIFT");
+        return static_cast<uint32_t>(e && *e ? std::min(2, std::max(0, atoi(e))) : 2);
+    }();
+    return shift;
+}
+
+template <int NT, int LT>
+void launch_digest_check_k(const DigestCheckArgs &a, uint32_t grid, hipStream_t s) {
+    hipLaunchKernelGGL((digest_check_kernel<NT, LT>), dim3(grid), dim3(kBlock), 0, s, a);
+}
+
+Capacity launch_digest_check(int k, int lt, const DigestCheckArgs &a, uint32_t grid, hipStream_t s) {
+#define CEC_DC(NT, LT)                            \
+    launch_digest_check_k<NT, LT>(a, grid, s);    \
+    return {NT, LT};
+    CEC_CAPACITY_RUNGS_FROM_4(k, lt, CEC_DC)
+#undef CEC_DC
+}
+
+}  // namespace
+
+static_assert(CEC_DIGEST_BYTES == kDigestBytes, "digest size");
+static_assert(CEC_KERNEL_DIGEST == 4 && CEC_KERNEL_DIGEST_CHECK == 5, "cec_launch_record::kind");
+static_assert(CEC_MAX_K + CEC_MAX_M == kDigestArenas && kDigestArenas == kScrubStreams, "a whole group per launch");
+
+static int digest_common(const char *op, int n, const uint8_t *const *arenas, uint8_t *const *digests,
+                         const cec_plan *plan, uint64_t len, void *stream_) {
+    if (!arenas || !digests) return fail(CEC_EINVAL, "%s: NULL arena or digest array", op);
+    if (n < 1 || n > kDigestArenas) return fail(CEC_EINVAL, "%s: n = %d outside [1, %d]", op, n, kDigestArenas);
+    for (int i = 0; i < n; ++i) {
+        if (!arenas[i]) return fail(CEC_EINVAL, "%s: arenas[%d] is NULL", op, i);
+        if (!digests[i]) return fail(CEC_EINVAL, "%s: digests[%d] is NULL", op, i);
+        if (reinterpret_cast<uintptr_t>(digests[i]) & 15)
+            return fail(CEC_EINVAL, "%s: digests[%d] is not 16-byte aligned", op, i);
+    }
+    int dev;
+    if (int r = current_device(&dev)) return r;
+    TileSource src;
+    if (int r = plan ? TileSource::of_plan(plan, dev, &src) : TileSource::of_region(len, &src)) return r;
+    t_last_engine = CEC_ENGINE_PERM;  // whatever cec_set_engine says
+    if (src.n_tiles == 0) return CEC_OK;
+    const uint64_t n_work = src.n_tiles * static_cast<uint64_t>(n);
+    if (n_work > kDigestMaxWork)
+        return fail(CEC_EINVAL, "%s: %llu tiles x %d arenas, one launch holds %llu (tile, arena) pairs", op,
+                    static_cast<unsigned long long>(src.n_tiles), n, static_cast<unsigned long long>(kDigestMaxWork));
+    if (int rc = launch_countdown()) return rc;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    DigestArgs a;
+    memset(&a, 0, sizeof a);
+    for (int i = 0; i < n; ++i) {
+        a.base[i] = arenas[i];
+        a.out[i] = digests[i];
+    }
+    a.tiles = src.tiles;
+    a.implicit_len = src.implicit_len;
+    a.n_tiles = static_cast<uint32_t>(src.n_tiles);
+    a.n = static_cast<uint32_t>(n);
+    a.n_work = static_cast<uint32_t>(n_work);
+    a.waves_shift = digest_waves_shift();
+    const uint32_t per_wg = 1u << a.waves_shift;
+    const uint32_t grid = static_cast<uint32_t>((n_work + per_wg - 1) / per_wg);
+    hipLaunchKernelGGL(digest_kernel, dim3(grid), dim3(64u << a.waves_shift), 0, stream, a);
+    if (src.uses) src.uses->note(stream);
+    HIP_TRY(hipGetLastError());
+    record_launch(CEC_KERNEL_DIGEST, {n, 0}, kAccNone, false, 0, 0, grid, src.n_tiles, 0);
+    return CEC_OK;
+}
+
+CEC_API int cec_digest(int n, const uint8_t *const *arenas, uint8_t *const *digests, const cec_plan *plan,
+                       void *stream) {
+    if (!plan) return fail(CEC_EINVAL, "cec_digest: plan is NULL");
+    if (int r = single_pattern_plan(plan, "cec_digest")) return r;
+    return digest_common("cec_digest", n, arenas, digests, plan, 0, stream);
+}
+
+CEC_API int cec_digest_region(int n, const uint8_t *const *arenas, uint8_t *const *digests, size_t len,
+                              void *stream) {
+    return digest_common("cec_digest_region", n, arenas, digests, nullptr, len, stream);
+}
+
+// One launch: the digests of parities [p0, p0 + lt) against the k data digests, one lane
+// per unit.  Reads no arena and no tile: the source only counts the units.
+static int digest_check_launch(int dev, cec_scrub_report *s, int k, int m, const int *matrix,
+                               const uint8_t *const *data, const uint8_t *const *parity, int p0, int lt,
+                               const TileSource &src, hipStream_t stream) {
+    (void)m;
+    if (int rc = launch_countdown()) return rc;
+    const std::vector<Pattern> pats = scrub_patterns(k, matrix, p0, lt);
+    DigestCheckArgs a;
+    memset(&a, 0, sizeof a);
+    for (int j = 0; j < k; ++j) a.dig[j] = data[j];
+    for (int l = 0; l < lt; ++l) a.dig[k + l] = parity[p0 + l];
+    PatEntry *entry = nullptr;
+    if (int rc = pattern_tables(dev, pats, {}, stream, &entry)) return rc;
+    a.pattern = reinterpret_cast<const Pattern *>(entry->d);
+    a.words = s->d_buf + kScrubHead;
+    a.counter = s->d_buf;
+    a.n_units = static_cast<uint32_t>(src.n_tiles);  // (<= the report's max_tiles <= kScrubMaxTiles)
+    a.syn_shift = static_cast<uint32_t>(p0);
+    const uint32_t grid = (a.n_units + kBlock - 1) / kBlock;
+    const Capacity cap = launch_digest_check(k, lt, a, grid, stream);
+    s->uses.note(stream);
+    pattern_done(entry);
+    HIP_TRY(hipGetLastError());
+    record_launch(CEC_KERNEL_DIGEST_CHECK, cap, kAccAll, false, 0, 0, grid, src.n_tiles, 0);
+    return CEC_OK;
+}
+
+CEC_API int cec_scrub_digests(cec_scrub_report *s, int k, int m, const int *matrix,
+                              const uint8_t *const *data_digests, const uint8_t *const *parity_digests,
+                              const cec_plan *plan, void *stream) {
+    if (!plan) return fail(CEC_EINVAL, "cec_scrub_digests: plan is NULL");
+    if (int r = single_pattern_plan(plan, "cec_scrub_digests")) return r;
+    return scrub_common("cec_scrub_digests", true, s, k, m, matrix, data_digests, parity_digests, plan, 0, stream);
+}
+
+CEC_API int cec_scrub_digests_region(cec_scrub_report *s, int k, int m, const int *matrix,
+                                     const uint8_t *const *data_digests, const uint8_t *const *parity_digests,
+                                     size_t len, void *stream) {
+    return scrub_common("cec_scrub_digests_region", true, s, k, m, matrix, data_digests, parity_digests, nullptr, len,
+                        stream);
+}

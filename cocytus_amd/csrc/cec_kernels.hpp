@@ -581,4 +581,209 @@ __global__ __launch_bounds__(kBlock) void scrub_kernel(ScrubArgs a) {
     }
 }
 
+// ---------------------------------------------------------------- the digest kernels
+// cec_digest: a 32-byte GF(2^8)-linear digest of every tile of every arena, so that a
+// process that holds one shard can take part in a scrub by shipping 1/128 of its bytes.
+// A tile, zero-padded to 4 KiB, is 256 chunks c_0..c_255 of 16 bytes; per byte column
+//     D0 = XOR_i c_i          D1 = sum_i w_i * c_i,  w_i = the field element of byte value i
+// and the digest is D0 || D1 (cocytus_ec.h).  digest_kernel is a read-only reduction:
+// one wave per (tile, arena), work item g = tile g / n, arena g % n, so the n arenas of a
+// tile are read together as the combine kernels read them; a workgroup is 2^waves_shift
+// independent waves (four by default).  No LDS, no barrier, no atomics;
+// the wave's last lane writes the 32 bytes with plain stores (nothing to clear beforehand).
+//   * lane L holds chunks L, L + 64, L + 128, L + 192: four coalesced global_load_dwordx4
+//     (full tile, 16-B aligned base), else gather16 with the valid count: bytes past len
+//     read 0 and are never fetched;
+//   * in registers, with A = c0 ^ c1 ^ c2 ^ c3 (this lane's share of D0): w is GF(2)-linear
+//     in the bits of i, so the lane's share of D1 is  L * A  ^  0x40 * (c1 ^ c3)  ^
+//     0x80 * (c2 ^ c3)  =  L * A ^ 0x40 * ((c1 ^ c3) ^ 2 * (c2 ^ c3)).  L * x is the PERM
+//     lookup (three v_perm_b32 per dword) with the lane's own tables in VGPRs, read from
+//     kDigestLaneTabs (1,280 B, every wave reads the same lines); 0x40 * x the same lookup
+//     with compile-time tables;
+//   * what is left is a plain XOR reduction of 8 dwords over the 64 lanes: DPP inside a
+//     row of 16 (quad_perm, row_ror), row_bcast15 / row_bcast31 across rows; lane 63 ends
+//     with the total.
+constexpr int kDigestBytes = 32;
+constexpr int kDigestArenas = 24;  // as kScrubStreams: a whole group in one launch
+
+struct DigestLaneTabs {
+    uint32_t w[5][64];  // w[.][L]: PermTab of coefficient L, one 256-B line per table word
+};
+constexpr DigestLaneTabs make_digest_lane_tabs() {
+    DigestLaneTabs t{};
+    for (int l = 0; l < 64; ++l) {
+        const PermTab p = make_perm_tab(l);
+        for (int w = 0; w < 5; ++w) t.w[w][l] = p.w[w];
+    }
+    return t;
+}
+static __device__ const DigestLaneTabs kDigestLaneTabs = make_digest_lane_tabs();
+
+struct DigestArgs {
+    const uint8_t *base[kDigestArenas];
+    uint8_t *out[kDigestArenas];  // out[a] + 32 * t: digest of tile t of base[a]; 16-B aligned
+    const Tile *tiles;            // NULL: implicit region [0, implicit_len)
+    uint64_t implicit_len;
+    uint32_t n_tiles;
+    uint32_t n;                   // arenas, 1..kDigestArenas
+    uint32_t n_work;              // n_tiles * n
+    uint32_t waves_shift;         // 2^waves_shift waves (work items) per workgroup
+};
+
+// 2 * x on four packed bytes
+__device__ inline uint32_t xtime4(uint32_t x) {
+    return ((x & 0x7F7F7F7Fu) << 1) ^ (((x >> 7) & 0x01010101u) * 0x1Du);
+}
+// the PERM lookup with tables in registers (PermEngine::mul reads them with scalar loads)
+__device__ inline uint32_t perm_mul(uint32_t x, const uint32_t (&t)[5]) {
+    const PermEngine::Sel s = PermEngine::sel(x);
+    return __builtin_amdgcn_perm(t[1], t[0], s.s0) ^ __builtin_amdgcn_perm(t[3], t[2], s.s1) ^
+           __builtin_amdgcn_perm(t[4], t[4], s.s2);
+}
+// x ^ (x of the lane the DPP control names); rows outside kRowMask keep x
+template <int kCtrl, int kRowMask = 0xF>
+__device__ inline uint32_t dpp_xor(uint32_t x) {
+    return x ^ static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), kCtrl, kRowMask, 0xF, false));
+}
+// XOR over the wave's 64 lanes; the total is in lane 63 (every lane must be active)
+__device__ inline uint32_t wave_xor_to_last(uint32_t x) {
+    x = dpp_xor<0xB1>(x);        // quad_perm [1,0,3,2]
+    x = dpp_xor<0x4E>(x);        // quad_perm [2,3,0,1]
+    x = dpp_xor<0x124>(x);       // row_ror:4
+    x = dpp_xor<0x128>(x);       // row_ror:8: every lane holds its row's total
+    x = dpp_xor<0x142, 0xA>(x);  // row_bcast15: rows 1, 3 ^= rows 0, 2
+    x = dpp_xor<0x143, 0xC>(x);  // row_bcast31: row 3 ^= row 1
+    return x;
+}
+
+__global__ __launch_bounds__(kBlock) void digest_kernel(DigestArgs a) {
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t g = (blockIdx.x << a.waves_shift) + wave;
+    if (g >= a.n_work) return;  // (wave-uniform)
+    const uint32_t t = g / a.n;
+    const uint32_t ar = g - t * a.n;
+    const uint32_t lane = threadIdx.x & 63u;
+    const TileRef tr = load_tile(a, t);
+    const uint8_t *in = a.base[ar] + tr.off;
+
+    uint4 c[4];
+    if ((reinterpret_cast<uint64_t>(in) & 15) == 0 && tr.len == kTile) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) c[j] = ld16(in, (lane + 64u * j) * 16u);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t pos = (lane + 64u * j) * 16u;
+            c[j] = make_uint4(0, 0, 0, 0);
+            if (pos < tr.len) c[j] = gather16(in, pos, min(16u, tr.len - pos));
+        }
+    }
+    uint32_t tab[5];
+#pragma unroll
+    for (int w = 0; w < 5; ++w) tab[w] = kDigestLaneTabs.w[w][lane];
+    constexpr PermTab k40 = make_perm_tab(0x40);
+    const uint32_t t40[5] = {k40.w[0], k40.w[1], k40.w[2], k40.w[3], k40.w[4]};
+
+    const uint32_t cw[4][4] = {{c[0].x, c[0].y, c[0].z, c[0].w}, {c[1].x, c[1].y, c[1].z, c[1].w},
+                               {c[2].x, c[2].y, c[2].z, c[2].w}, {c[3].x, c[3].y, c[3].z, c[3].w}};
+    uint32_t d[8];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const uint32_t hi6 = cw[1][w] ^ cw[3][w];  // chunks whose index has bit 6
+        const uint32_t hi7 = cw[2][w] ^ cw[3][w];  // ... bit 7
+        const uint32_t A = cw[0][w] ^ cw[2][w] ^ hi6;
+        d[w] = A;
+        d[4 + w] = perm_mul(A, tab) ^ perm_mul(hi6 ^ xtime4(hi7), t40);
+    }
+#pragma unroll
+    for (int w = 0; w < 8; ++w) d[w] = wave_xor_to_last(d[w]);
+    if (lane == 63) {
+        CEC_GLOBAL u32x4 *o = (CEC_GLOBAL u32x4 *)((uintptr_t)a.out[ar] + static_cast<uint64_t>(t) * kDigestBytes);
+        u32x4 v0, v1;
+        v0.x = d[0]; v0.y = d[1]; v0.z = d[2]; v0.w = d[3];
+        v1.x = d[4]; v1.y = d[5]; v1.z = d[6]; v1.w = d[7];
+        o[0] = v0;
+        o[1] = v1;
+    }
+}
+
+// cec_scrub_digests: the scrub's syndrome and ratio test on the digests.  The digest is
+// linear and commutes with scalars, so digest(S_p) is the syndrome of the digests and
+// digest(ratio * S_0 ^ S_q) their ratio test: the report word has cec_scrub's exact meaning
+// (scrub_kernel above), and for corruption within two chunks of a tile its exact bits.
+// One lane per unit: it loads the 2 x 16 bytes of the k data digests and of the launch's
+// parity digests, runs compute_chunk on each half with scrub_launch's own two patterns,
+// and decides alone (a wave holds 64 different units: no ballot).  Capacity shapes only.
+struct DigestCheckArgs {
+    const uint8_t *dig[kScrubStreams];  // [0, k): data digests; [k, k + n_out): the launch's parity digests
+    const Pattern *pattern;             // [0]: coefficients; [1]: ratio tables
+    uint32_t *words;
+    uint32_t *counter;
+    uint32_t n_units;
+    uint32_t syn_shift;
+};
+
+// (default cache policy: both halves of a digest share a line)
+__device__ inline uint4 ld16_cached(const uint8_t *p) {
+    const u32x4 v = *(const CEC_GLOBAL u32x4 *)(uintptr_t)p;
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+template <int NT, int LT>
+__global__ __launch_bounds__(kBlock) void digest_check_kernel(DigestCheckArgs a) {
+    const uint32_t u = blockIdx.x * kBlock + threadIdx.x;
+    if (u >= a.n_units) return;
+    const CEC_CONST Pattern *P = as_const(a.pattern);
+    const int n_in = P->n_in;
+    const int n_out = P->n_out;
+    const uint64_t at = static_cast<uint64_t>(u) * kDigestBytes;
+    uint32_t word = 0;
+#pragma unroll 1
+    for (uint32_t h = 0; h < 2; ++h) {
+        uint4 x[NT];
+        uint4 acc[LT];
+#pragma unroll
+        for (int i = 0; i < NT; ++i)
+            if (i < n_in) x[i] = ld16_cached(a.dig[i] + at + 16 * h);
+#pragma unroll
+        for (int l = 0; l < LT; ++l) {
+            acc[l] = make_uint4(0, 0, 0, 0);
+            if (l < n_out) acc[l] = ld16_cached(a.dig[n_in + l] + at + 16 * h);
+        }
+        compute_chunk<NT, LT, PermEngine>(P, n_in, n_out, x, acc, nullptr);
+        uint32_t any = 0;
+#pragma unroll
+        for (int l = 0; l < LT; ++l) {
+            const uint32_t nz = acc[l].x | acc[l].y | acc[l].z | acc[l].w;  // (0 for l >= n_out)
+            if (nz) word |= 1u << (a.syn_shift + l);
+            any |= nz;
+        }
+        if constexpr (LT >= 2) {
+            if (any != 0 && n_out >= 2) {
+                const CEC_CONST Pattern *R = P + 1;
+                const PermEngine::Sel s0[4] = {PermEngine::sel(acc[0].x), PermEngine::sel(acc[0].y),
+                                               PermEngine::sel(acc[0].z), PermEngine::sel(acc[0].w)};
+#pragma unroll 1
+                for (int j = 0; j < n_in; ++j) {
+                    uint32_t differ = 0;
+#pragma unroll
+                    for (int q = 1; q < LT; ++q) {
+                        if (q >= n_out) continue;
+                        const CEC_CONST uint32_t *tb = R->tab[q][j];
+                        differ |= (PermEngine::mul(s0[0], tb, nullptr) ^ acc[q].x) |
+                                  (PermEngine::mul(s0[1], tb, nullptr) ^ acc[q].y) |
+                                  (PermEngine::mul(s0[2], tb, nullptr) ^ acc[q].z) |
+                                  (PermEngine::mul(s0[3], tb, nullptr) ^ acc[q].w);
+                    }
+                    if (differ) word |= 1u << (8 + j);
+                }
+            }
+        }
+    }
+    if (word & 0xFFu) {
+        const uint32_t old = atomicOr(a.words + u, word);
+        if ((old & 0xFFu) == 0) atomicAdd(a.counter, 1u);
+    }
+}
+
 }  // namespace cec

@@ -553,8 +553,8 @@ static_assert(kFlagSysRelease == CEC_LAUNCH_SYS_RELEASE && kFlagWriteThrough == 
               "cec_launch_record::flags");
 
 // The calling thread's last enqueued kernel launch (cec_last_launch).  record_launch is
-// the one place that writes it: launch_combine and scrub_launch, the library's two
-// launch routines, each call it once per kernel they enqueue.
+// the one place that writes it: launch_combine, scrub_launch and the two digest launches
+// (cec_digest.inc), the library's launch routines, each call it once per kernel they enqueue.
 static thread_local cec_launch_record t_last_launch = {0, -1, 0, 0, -1, -1, 0, 0, 0, 0, 0};
 
 static void record_launch(int kind, Capacity cap, int acc, bool lds, uint32_t split_shift, uint32_t flags,
@@ -571,7 +571,8 @@ CEC_API int cec_last_launch(cec_launch_record *out) {
 
 // Test hook (cec_internal_fail_launch): the calling thread's next `after` launches run, the
 // one after them is refused as a HIP failure, then the hook disarms.  -1: off.
-// Counted by run_combine and scrub_launch (launch_countdown), before anything is built.
+// Counted by run_combine, scrub_launch and the digest launches (launch_countdown), before
+// anything is built.
 static thread_local int t_fail_after = -1;
 CEC_API int cec_internal_fail_launch(int after) {
     t_fail_after = after < 0 ? -1 : after;
@@ -1382,6 +1383,7 @@ CEC_API int cec_last_sync(cec_sync_record *out) {
 #include "cec_pool.inc"
 #include "cec_hostbatch.inc"
 #include "cec_scrub.inc"
+#include "cec_digest.inc"
 
 // ============================================================== events / streams
 CEC_API int cec_event_create(void **ev) {

@@ -106,13 +106,12 @@ CEC_API int cec_scrub_release_stream(cec_scrub_report *s, void *stream) {
     return CEC_OK;
 }
 
-// One launch: parities [p0, p0 + lt) of the code against the k data streams.
-static int scrub_launch(int dev, cec_scrub_report *s, int k, int m, const int *matrix, const uint8_t *const *data,
-                        const uint8_t *const *parity, int p0, int lt, const TileSource &src, hipStream_t stream) {
-    if (int rc = launch_countdown()) return rc;
-    // [0]: the syndrome's coefficients; [1]: ratio[q][j] = MATRIX(k+p0+q, j) / MATRIX(k+p0, j)
-    // as PERM tables (a zero denominator leaves the zero table: lid j is then ruled out
-    // wherever S_q is non-zero, which errs towards UNLOCATED)
+// The two patterns of one launch over parities [p0, p0 + lt) of the code, for the arena
+// scrub and for the digest check (cec_digest.inc) alike:
+// [0]: the syndrome's coefficients; [1]: ratio[q][j] = MATRIX(k+p0+q, j) / MATRIX(k+p0, j)
+// as PERM tables (a zero denominator leaves the zero table: lid j is then ruled out
+// wherever S_q is non-zero, which errs towards UNLOCATED)
+static std::vector<Pattern> scrub_patterns(int k, const int *matrix, int p0, int lt) {
     std::vector<Pattern> pats(2, blank_pattern());
     Pattern &c = pats[0], &r = pats[1];
     c.n_in = r.n_in = k;
@@ -127,6 +126,14 @@ static int scrub_launch(int dev, cec_scrub_report *s, int k, int m, const int *m
             set_coef(r, l, j, l && den ? gf_div(MATRIX(k + p0 + l, j), den) : 0, CEC_ENGINE_PERM);
         }
     }
+    return pats;
+}
+
+// One launch: parities [p0, p0 + lt) of the code against the k data streams.
+static int scrub_launch(int dev, cec_scrub_report *s, int k, int m, const int *matrix, const uint8_t *const *data,
+                        const uint8_t *const *parity, int p0, int lt, const TileSource &src, hipStream_t stream) {
+    if (int rc = launch_countdown()) return rc;
+    const std::vector<Pattern> pats = scrub_patterns(k, matrix, p0, lt);
     ScrubArgs a;
     memset(&a, 0, sizeof a);
     Streams st;  // (for split_shift_for: every base of the launch)
@@ -153,18 +160,39 @@ static int scrub_launch(int dev, cec_scrub_report *s, int k, int m, const int *m
     return CEC_OK;
 }
 
-static int scrub_common(cec_scrub_report *s, int k, int m, const int *matrix, const uint8_t *const *data,
-                        const uint8_t *const *parity, const cec_plan *plan, uint64_t len, void *stream_) {
+// One launch of the digest check (cec_digest.inc), with scrub_launch's arguments.
+static int digest_check_launch(int dev, cec_scrub_report *s, int k, int m, const int *matrix,
+                               const uint8_t *const *data, const uint8_t *const *parity, int p0, int lt,
+                               const TileSource &src, hipStream_t stream);
+
+// cec_scrub and cec_scrub_digests: clear the report, one launch per four parities, copy
+// the counter back.  `digests`: data / parity are the group's digest arrays (32 B per tile)
+// and the launches are digest_check_launch's; the plan or len then only counts the tiles
+// and gives each finding its off / len.
+static int scrub_common(const char *op, bool digests, cec_scrub_report *s, int k, int m, const int *matrix,
+                        const uint8_t *const *data, const uint8_t *const *parity, const cec_plan *plan, uint64_t len,
+                        void *stream_) {
+    const char *what = digests ? " digests" : "";
     if (int r = check_code(k, m, matrix)) return r;
-    if (!data || !parity) return fail(CEC_EINVAL, "cec_scrub: NULL arena array");
+    if (!data || !parity) return fail(CEC_EINVAL, "%s: NULL %s array", op, digests ? "digest" : "arena");
     for (int j = 0; j < k; ++j)
-        if (!data[j]) return fail(CEC_EINVAL, "cec_scrub: data[%d] is NULL", j);
+        if (!data[j]) return fail(CEC_EINVAL, "%s: data%s[%d] is NULL", op, what, j);
     for (int p = 0; p < m; ++p)
-        if (!parity[p]) return fail(CEC_EINVAL, "cec_scrub: parity[%d] is NULL (a lost parity cannot be checked)", p);
-    if (!s) return fail(CEC_EINVAL, "cec_scrub: report is NULL");
+        if (!parity[p])
+            return fail(CEC_EINVAL, "%s: parity%s[%d] is NULL (a lost parity cannot be checked)", op, what, p);
+    if (digests) {
+        if (!s) {  // no report can exist without a device: say that first (CEC_ENODEV)
+            int none;
+            if (int r = current_device(&none)) return r;
+        }
+        for (int i = 0; i < k + m; ++i)
+            if (reinterpret_cast<uintptr_t>(i < k ? data[i] : parity[i - k]) & 15)
+                return fail(CEC_EINVAL, "%s: digest array of lid %d is not 16-byte aligned", op, i);
+    }
+    if (!s) return fail(CEC_EINVAL, "%s: report is NULL", op);
     const uint64_t n_tiles = plan ? static_cast<uint64_t>(plan->n_tiles) : (len + kTile - 1) / kTile;
     if (n_tiles > s->max_tiles)
-        return fail(CEC_EINVAL, "cec_scrub: %llu tiles, the report holds %llu",
+        return fail(CEC_EINVAL, "%s: %llu tiles, the report holds %llu", op,
                     static_cast<unsigned long long>(n_tiles), static_cast<unsigned long long>(s->max_tiles));
     int dev;
     if (int r = current_device(&dev)) return r;
@@ -178,7 +206,8 @@ static int scrub_common(cec_scrub_report *s, int k, int m, const int *matrix, co
     HIP_TRY(hipMemsetAsync(s->d_buf, 0, sizeof(uint32_t) * (kScrubHead + n_tiles), stream));
     if (n_tiles)
         for (int p0 = 0; p0 < m; p0 += kPatL)
-            if (int r = scrub_launch(dev, s, k, m, matrix, data, parity, p0, std::min<int>(kPatL, m - p0), src, stream))
+            if (int r = (digests ? digest_check_launch : scrub_launch)(dev, s, k, m, matrix, data, parity, p0,
+                                                                       std::min<int>(kPatL, m - p0), src, stream))
                 return r;
     HIP_TRY(hipMemcpyAsync(s->h_buf, s->d_buf, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     s->stream = stream;
@@ -196,12 +225,12 @@ CEC_API int cec_scrub(cec_scrub_report *s, int k, int m, const int *matrix, cons
                       const uint8_t *const *parity, const cec_plan *plan, void *stream) {
     if (!plan) return fail(CEC_EINVAL, "cec_scrub: plan is NULL");
     if (int r = single_pattern_plan(plan, "cec_scrub")) return r;
-    return scrub_common(s, k, m, matrix, data, parity, plan, 0, stream);
+    return scrub_common("cec_scrub", false, s, k, m, matrix, data, parity, plan, 0, stream);
 }
 
 CEC_API int cec_scrub_region(cec_scrub_report *s, int k, int m, const int *matrix, const uint8_t *const *data,
                              const uint8_t *const *parity, size_t len, void *stream) {
-    return scrub_common(s, k, m, matrix, data, parity, nullptr, len, stream);
+    return scrub_common("cec_scrub", false, s, k, m, matrix, data, parity, nullptr, len, stream);
 }
 
 CEC_API int64_t cec_scrub_wait(cec_scrub_report *s) {

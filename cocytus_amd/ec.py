@@ -117,6 +117,9 @@ class LaunchRecord(ctypes.Structure):
 
 CEC_KERNEL_NARROW, CEC_KERNEL_EXACT, CEC_KERNEL_GENERIC = 0, 1, 2
 CEC_KERNEL_SCRUB = 3  # cec_scrub's read-only kernel
+CEC_KERNEL_DIGEST = 4  # cec_digest's reduction (nt = the arenas of the launch, lt = 0)
+CEC_KERNEL_DIGEST_CHECK = 5  # cec_scrub_digests: the scrub's test, one lane per unit
+DIGEST_BYTES = 32  # CEC_DIGEST_BYTES: per 4 KiB unit
 CEC_SCRUB_UNLOCATED = -1
 
 
@@ -214,6 +217,10 @@ _SIGS = {
     "cec_scrub_findings": ([_vp, ctypes.POINTER(ScrubFinding), _i], _i),
     "cec_scrub_classify": ([_u32, _i, _i, _ip], _i),
     "cec_scrub_repair": ([_vp, _i, _i, _ip, _pp, _pp, _vp, _ip], _i),
+    "cec_digest": ([_i, _pp, _pp, _vp, _vp], _i),
+    "cec_digest_region": ([_i, _pp, _pp, ctypes.c_size_t, _vp], _i),
+    "cec_scrub_digests": ([_vp, _i, _i, _ip, _pp, _pp, _vp, _vp], _i),
+    "cec_scrub_digests_region": ([_vp, _i, _i, _ip, _pp, _pp, ctypes.c_size_t, _vp], _i),
     "cec_cache_get_info": ([ctypes.POINTER(CacheInfo)], _i),
     "cec_last_sync": ([ctypes.POINTER(SyncRecord)], _i),
     "cec_last_launch": ([ctypes.POINTER(LaunchRecord)], _i),
@@ -570,6 +577,23 @@ def decode(k, m, matrix, masks: Sequence[int], arenas, out, plan: Plan, stream=N
                             _ptr_array(out), plan.handle, _stream(stream)))
 
 
+def digest(arenas, digests, plan: Plan, stream=None) -> None:
+    """cec_digest: digests[a][32 t : 32 t + 32] = digest of tile t of arenas[a]; one launch for
+    all the arenas given (1..24); async on stream.  Digest arrays are 16-byte aligned."""
+    arenas, digests = list(arenas), list(digests)
+    if len(arenas) != len(digests):
+        raise ValueError("one digest array per arena")
+    _check(lib().cec_digest(len(arenas), _ptr_array(arenas), _ptr_array(digests), plan.handle, _stream(stream)))
+
+
+def digest_region(arenas, digests, length: int, stream=None) -> None:
+    """cec_digest_region: cec_digest over the implicit 4 KiB tiling of [0, length)."""
+    arenas, digests = list(arenas), list(digests)
+    if len(arenas) != len(digests):
+        raise ValueError("one digest array per arena")
+    _check(lib().cec_digest_region(len(arenas), _ptr_array(arenas), _ptr_array(digests), length, _stream(stream)))
+
+
 def recovery_mask(k: int, m: int, leader_lid: int, connected: Sequence[int]) -> int:
     return lib().cec_recovery_mask(k, m, leader_lid, _int_array(connected))
 
@@ -854,6 +878,16 @@ class Scrub:
     def run_region(self, k, m, matrix, data, parity, length: int, stream=None) -> None:
         _check(lib().cec_scrub_region(self._h, k, m, _int_array(matrix), _ptr_array(data),
                                       _ptr_array(parity), length, _stream(stream)))
+
+    def run_digests(self, k, m, matrix, data_digests, parity_digests, plan: Plan, stream=None) -> None:
+        """cec_scrub_digests: the scrub over the group's digest arrays (ec.digest); the plan
+        is the one the digests were taken over.  wait / findings / repair as after run()."""
+        _check(lib().cec_scrub_digests(self._h, k, m, _int_array(matrix), _ptr_array(data_digests),
+                                       _ptr_array(parity_digests), plan.handle, _stream(stream)))
+
+    def run_digests_region(self, k, m, matrix, data_digests, parity_digests, length: int, stream=None) -> None:
+        _check(lib().cec_scrub_digests_region(self._h, k, m, _int_array(matrix), _ptr_array(data_digests),
+                                              _ptr_array(parity_digests), length, _stream(stream)))
 
     def wait(self) -> int:
         n = lib().cec_scrub_wait(self._h)

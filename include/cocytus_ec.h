@@ -451,6 +451,11 @@ int cec_recovery_pool_active(const cec_recovery_pool *pool);
  * syndrome decoder.  m = 1 detects but never locates.  The location rests on the MDS
  * property of the matrices reed_sol_big_vandermonde_distribution_matrix returns: non-zero
  * parity coefficients whose ratios between two parity rows differ from column to column.
+ * The scrub over digests (cec_scrub_digests, below) adds one limit of its own: corruption
+ * of three or more 16-byte chunks of a tile in one byte column can cancel in the digest --
+ * errors (1, 2, 3) * v in chunks 1, 2, 3 do -- and is then not seen at all; random
+ * corruption of that kind is missed with probability 2^-16 per column.  Corruption within
+ * one or two chunks of a tile is always seen, and reported exactly as cec_scrub reports it.
  *
  * A cec_scrub_report is reusable (device words + counter, pinned mirror) for runs of up to
  * max_tiles tiles; at most 0xFFFFFFFF / 256 tiles (64 GiB per arena), one dispatch.  (The
@@ -501,6 +506,67 @@ int cec_scrub_classify(uint32_t word, int k, int m, const int *matrix);
  * cec_scrub again to confirm. */
 int cec_scrub_repair(cec_scrub_report *s, int k, int m, const int *matrix, uint8_t *const *data,
                      uint8_t *const *parity, void *stream, int *unrepaired);
+
+/* ---- unit digests: the scrub across processes ----
+ * Cocytus runs one process per shard, each with its own arena on its own host, so no
+ * process can call cec_scrub (PLACEMENT above).  The code is linear over GF(2^8); a digest
+ * that is linear over GF(2^8) as well commutes with it,
+ *     digest(parity_p) = sum_j MATRIX(k+p, j) * digest(data_j),
+ * (homomorphic fingerprinting).  Each process digests its own arena on its own device,
+ * CEC_DIGEST_BYTES per 4 KiB unit (1/128 of the bytes), ships the digests, and the leader
+ * runs the scrub's syndrome and ratio test on them: the same cec_scrub_report, the same
+ * wait / findings / classify, and a located unit goes to the recovery path.
+ *
+ * THE DIGEST.  Field: this library's (polynomial 0x11D).  A tile (a piece of an extent
+ * that ends on a 4 KiB arena boundary, len = 1..4096, as cec_plan_create and the implicit
+ * region make them) is padded with zeros to 4096 bytes and read as 256 chunks c_0..c_255 of
+ * 16 bytes, chunk i = bytes [16 i, 16 i + 16) from the tile's first byte.  For each of the
+ * 16 byte columns t:
+ *     D0[t] = XOR_i c_i[t]
+ *     D1[t] = sum_i w_i * c_i[t],   w_i = the field element whose byte value is i
+ * digest = D0 || D1.  The digest of tile t of a plan or region is at digests + 32 * t.
+ * GUARANTEE: the 256 weights are distinct, so per column the digest is a distance-3 code:
+ * any corruption confined to one or two chunks of a tile changes the digest, with
+ * certainty, and for such corruption the report word of cec_scrub_digests equals cec_scrub's
+ * bit for bit (digest(S_p) is the syndrome of the digests, digest(ratio * S_0 ^ S_q) their
+ * ratio test).  LIMIT (beside the ASSUMPTION above): corruption of three or more chunks in
+ * one column can cancel -- errors (1, 2, 3) * v in chunks 1, 2, 3 of one column lie in the
+ * digest's null space; random corruption of that kind is missed with probability 2^-16,
+ * 2^-16c over c columns.
+ *
+ * SNAPSHOT RULE: the digests of a group must be taken with every shard at the same stable
+ * xid, in the idle loop -- the condition cec_scrub's idle-loop placement already assumes.
+ * Out of scope: keeping digests current on each SET (linearity allows
+ * digest ^= digest(diff) later); every call here digests the bytes as they are.
+ *
+ * cec_digest: digests[a] + 32 * t = digest of tile t of arenas[a], for n arenas (1..24: a
+ * whole group, or a process's own) in one launch; async on `stream`.  Read-only on the
+ * arenas; bytes outside the tiles are never fetched.  Every digest is written with plain
+ * stores (no clear beforehand; a re-run overwrites).  Checked as cec_scrub checks: NULL
+ * arrays or entries and n outside [1, 24] are CEC_EINVAL, the plan's device is checked and
+ * its extent patterns must be 0, no device is CEC_ENODEV; digest arrays must be 16-byte
+ * aligned (CEC_EINVAL), and tiles x n is at most 67,108,860 per call.  An empty plan or
+ * len == 0 launches nothing and returns CEC_OK.  ENGINE: PERM arithmetic, as cec_scrub. */
+#define CEC_DIGEST_BYTES 32
+int cec_digest(int n, const uint8_t *const *arenas, uint8_t *const *digests,
+               const cec_plan *plan, void *stream);
+int cec_digest_region(int n, const uint8_t *const *arenas, uint8_t *const *digests,
+                      size_t len, void *stream);
+/* The scrub over digests (device arrays of 32 B per unit, 16-byte aligned): the sequence,
+ * refusals and validity rules of cec_scrub -- clear the report, one launch per four
+ * parities, copy the counter back; more units than the report holds or a NULL (lost)
+ * parity digest array is CEC_EINVAL; a failed run leaves the report invalid.  `plan` / `len`
+ * describe the units the digests were taken over: they give the unit count and each
+ * finding's off / len; no arena is read.  Sets the same fields of the report, so
+ * cec_scrub_wait / _findings / _repair work after it unchanged.  cec_scrub_repair still
+ * needs the arenas on this device: it is the single-device convenience; a distributed
+ * server takes each finding's lid and unit to its recovery path. */
+int cec_scrub_digests(cec_scrub_report *s, int k, int m, const int *matrix,
+                      const uint8_t *const *data_digests, const uint8_t *const *parity_digests,
+                      const cec_plan *plan, void *stream);
+int cec_scrub_digests_region(cec_scrub_report *s, int k, int m, const int *matrix,
+                             const uint8_t *const *data_digests, const uint8_t *const *parity_digests,
+                             size_t len, void *stream);
 
 /* ---- process-wide caches ----
  * Coefficient tables are uploaded once per distinct content (asynchronously, on the
@@ -554,7 +620,11 @@ int cec_last_sync(cec_sync_record *out);
  * first launch seq is 0 and kind / acc / engine are -1. */
 enum { CEC_KERNEL_NARROW = 0, CEC_KERNEL_EXACT = 1, CEC_KERNEL_GENERIC = 2,
        CEC_KERNEL_SCRUB = 3 /* cec_scrub's read-only kernel: nt = k or its capacity {4,8,16}, lt = the
-                             * launch's parities or their capacity {1,2,4}, acc = CEC_ACC_ALL, PERM */ };
+                             * launch's parities or their capacity {1,2,4}, acc = CEC_ACC_ALL, PERM */,
+       CEC_KERNEL_DIGEST = 4 /* cec_digest: nt = the arenas of the launch, lt = 0, acc = CEC_ACC_NONE,
+                              * split_shift 0, PERM, flags 0 */,
+       CEC_KERNEL_DIGEST_CHECK = 5 /* cec_scrub_digests: nt / lt = the capacities {4,8,16} x {1,2,4},
+                                    * acc = CEC_ACC_ALL, PERM, flags 0 */ };
 enum { CEC_ACC_NONE = 0, CEC_ACC_ALL = 1, CEC_ACC_ALL_BUT_LAST = 2, CEC_ACC_RUNTIME = 3 };
 enum { CEC_LAUNCH_SYS_RELEASE = 1, CEC_LAUNCH_WRITE_THROUGH = 2 };
 typedef struct cec_launch_record {
