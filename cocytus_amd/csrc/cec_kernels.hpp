@@ -88,9 +88,14 @@ constexpr uint32_t kFlagSysRelease = 1u;
 // dirty lines they would leave in L2 are a visible part of the launch (DESIGN.md §4:
 // the per-GPU shares of strong scaling).
 constexpr uint32_t kFlagWriteThrough = 2u;
+// CombineArgsN::flags, for the launch record only: the launch has a write-through tail
+// (CombineArgs::wt_from names a work item).  The kernel reads wt_from, not this bit.
+constexpr uint32_t kFlagWtTail = 4u;
+
+constexpr int kNarrowStreams = 2;
 
 template <int S>
-struct CombineArgsN {
+struct CombineArgsCore {
     uint8_t *base[S];
     const Tile *tiles;       // NULL: implicit region [0, implicit_len), pattern 0
     const Pattern *patterns;
@@ -101,8 +106,19 @@ struct CombineArgsN {
     uint32_t grid;         // workgroups in the launch (the grid-stride step)
     uint32_t flags;        // kFlag* bits (fills the struct's padding)
 };
+// The full block adds the write-through tail: work items g >= wt_from store as a
+// kFlagWriteThrough launch does, the ones before them non-temporally (kNoWtTail: none).
+// It comes last, so every other field keeps its offset.  The narrow block does not carry it:
+// narrow launches are small and write through as a whole.
+constexpr uint64_t kNoWtTail = ~uint64_t(0);
+template <int S>
+struct CombineArgsN : CombineArgsCore<S> {
+    uint64_t wt_from;
+};
+template <>
+struct CombineArgsN<kNarrowStreams> : CombineArgsCore<kNarrowStreams> {};
 using CombineArgs = CombineArgsN<kMaxStreams>;
-constexpr int kNarrowStreams = 2;
+static_assert(sizeof(CombineArgsN<kNarrowStreams>) == 64, "the narrow kernels' argument block must not grow");
 
 #define CEC_CONST __attribute__((address_space(4)))
 #define CEC_GLOBAL __attribute__((address_space(1)))
@@ -429,7 +445,12 @@ __global__ __launch_bounds__(kBlock) void combine_kernel(CombineArgsN<S> a) {
         if (wide) {
             // (the LDS engine keeps non-temporal stores: the branch alone cost its encode
             // 1 %, profiles/r03_evidence/lds_engine_ab/)
-            if (!Eng::kStaged && (a.flags & kFlagWriteThrough)) {
+            bool wt = false;
+            if constexpr (!Eng::kStaged) {
+                wt = (a.flags & kFlagWriteThrough) != 0;
+                if constexpr (S > kNarrowStreams) wt = wt || g >= a.wt_from;  // (uniform: g is the work item)
+            }
+            if (wt) {
 #pragma unroll
                 for (int l = 0; l < LT; ++l)
                     if (l < n_out) st16_wt(out[l], pos, acc[l]);

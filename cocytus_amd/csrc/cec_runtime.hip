@@ -495,9 +495,9 @@ static const int g_store_policy = [] {
     fprintf(stderr, "libcocytus_ec: CEC_STORE_POLICY=%s is not nt, wt or auto; using auto\n", e);
     return static_cast<int>(kStoreAuto);
 }();
-static const uint64_t g_wt_max_bytes = [] {
-    const uint64_t dflt = uint64_t(512) << 20;
-    const char *e = getenv("CEC_WT_MAX_BYTES");
+// A byte count from the environment; a bad value is reported on stderr once and ignored.
+static uint64_t parse_byte_count(const char *name, uint64_t dflt) {
+    const char *e = getenv(name);
     if (!e || !*e) return dflt;
     // strtoull alone would take "-1" as 2^64 - 1 and skip leading blanks: a byte count is
     // digits only (decimal, 0x hex or 0 octal), in range
@@ -505,20 +505,54 @@ static const uint64_t g_wt_max_bytes = [] {
     errno = 0;
     const unsigned long long v = (*e >= '0' && *e <= '9') ? strtoull(e, &end, 0) : 0;
     if (!(*e >= '0' && *e <= '9') || !end || *end || errno == ERANGE) {
-        fprintf(stderr, "libcocytus_ec: CEC_WT_MAX_BYTES=%s is not a byte count; using %llu\n", e,
+        fprintf(stderr, "libcocytus_ec: %s=%s is not a byte count; using %llu\n", name, e,
                 static_cast<unsigned long long>(dflt));
         return dflt;
     }
     return static_cast<uint64_t>(v);
-}();
+}
+static const uint64_t g_wt_max_bytes = parse_byte_count("CEC_WT_MAX_BYTES", uint64_t(512) << 20);
 // The store policy in force (tests: every kernel kind runs under each).
 CEC_API int cec_internal_store_policy(uint64_t *wt_max_bytes) {
     if (wt_max_bytes) *wt_max_bytes = g_wt_max_bytes;
     return g_store_policy;
 }
-static bool write_through(uint64_t n_tiles, int streams) {
-    if (g_store_policy != kStoreAuto) return g_store_policy == kStoreWt;
-    return n_tiles * kTile * static_cast<uint64_t>(streams) <= g_wt_max_bytes;
+// A launch too large for write-through keeps non-temporal stores for its body and writes
+// its last g_wt_tail_bytes (all outputs together) through.  Plain bench step (RS(3,2),
+// 65,536 x 4 KiB, encode + rotating decode), 3 interleaved processes per tail on one box,
+// GiB/s (profiles/store_tail_ab.md): no tail 2553-2581, 32 MiB 2568-2610, 64 MiB
+// 2600-2634, 96 MiB 2643-2659, 128 MiB 2651-2666, 144 MiB 2647-2653, 160 MiB 2605-2612,
+// 192 MiB 2520-2529, 256 MiB 2431-2449: a plateau from 96 to 144 MiB, the smallest of it
+// taken.  The launch boundary is the same 5 us with and without (tools/trace_check.py):
+// the gain is in the kernels' own time, the last writes of a launch being taken up on
+// the memory side.  CEC_WT_TAIL_BYTES overrides (measurement); 0: no tail.
+static const uint64_t g_wt_tail_bytes = parse_byte_count("CEC_WT_TAIL_BYTES", uint64_t(96) << 20);
+
+// Which work items of a launch store write-through: all (the kFlagWriteThrough launch),
+// none, or those from `from` on.  `streamed`: the bytes the launch reads and writes.
+struct StoreChoice {
+    bool all;
+    uint64_t from;  // kNoWtTail: none
+};
+static StoreChoice write_through(uint64_t n_tiles, uint32_t split_shift, int lt, uint64_t streamed) {
+    if (g_store_policy != kStoreAuto) return {g_store_policy == kStoreWt, kNoWtTail};
+    if (streamed <= g_wt_max_bytes) return {true, kNoWtTail};
+    if (g_wt_tail_bytes == 0 || lt <= 0) return {false, kNoWtTail};
+    const uint64_t per_item = static_cast<uint64_t>(lt) * (kTile >> split_shift);  // bytes one work item writes
+    const uint64_t items = g_wt_tail_bytes / per_item + (g_wt_tail_bytes % per_item != 0);
+    const uint64_t n_work = n_tiles << split_shift;
+    if (items >= n_work) return {true, kNoWtTail};  // the tail is the whole launch
+    return {false, n_work - items};
+}
+// Test hook: the choice for a launch of n_tiles tiles, lt outputs, `streamed` bytes.
+// Returns 0 none, 1 a tail from *wt_from, 2 all.
+CEC_API int cec_internal_wt_from(uint64_t n_tiles, uint32_t split_shift, int lt, uint64_t streamed,
+                                 uint64_t *wt_tail_bytes, uint64_t *wt_from) {
+    if (split_shift > 2 || n_tiles > 0xFFFFFFFFull) return fail(CEC_EINVAL, "cec_internal_wt_from: bad args");
+    const StoreChoice c = write_through(n_tiles, split_shift, lt, streamed);
+    if (wt_tail_bytes) *wt_tail_bytes = g_wt_tail_bytes;
+    if (wt_from) *wt_from = c.from;
+    return c.all ? 2 : c.from != kNoWtTail ? 1 : 0;
 }
 
 // The kernel a pattern set takes: capacities, LDS rows, and the exact shape if every
@@ -549,18 +583,18 @@ static_assert(kKindNarrow == CEC_KERNEL_NARROW && kKindExact == CEC_KERNEL_EXACT
                   kKindGeneric == CEC_KERNEL_GENERIC, "cec_launch_record::kind");
 static_assert(kAccNone == CEC_ACC_NONE && kAccAll == CEC_ACC_ALL && kAccAllButLast == CEC_ACC_ALL_BUT_LAST &&
                   kAccRuntime == CEC_ACC_RUNTIME, "cec_launch_record::acc");
-static_assert(kFlagSysRelease == CEC_LAUNCH_SYS_RELEASE && kFlagWriteThrough == CEC_LAUNCH_WRITE_THROUGH,
-              "cec_launch_record::flags");
+static_assert(kFlagSysRelease == CEC_LAUNCH_SYS_RELEASE && kFlagWriteThrough == CEC_LAUNCH_WRITE_THROUGH &&
+                  kFlagWtTail == CEC_LAUNCH_WT_TAIL, "cec_launch_record::flags");
 
 // The calling thread's last enqueued kernel launch (cec_last_launch).  record_launch is
 // the one place that writes it: launch_combine, scrub_launch and the two digest launches
 // (cec_digest.inc), the library's launch routines, each call it once per kernel they enqueue.
-static thread_local cec_launch_record t_last_launch = {0, -1, 0, 0, -1, -1, 0, 0, 0, 0, 0};
+static thread_local cec_launch_record t_last_launch = {0, -1, 0, 0, -1, -1, 0, 0, 0, 0, 0, kNoWtTail};
 
 static void record_launch(int kind, Capacity cap, int acc, bool lds, uint32_t split_shift, uint32_t flags,
-                          uint32_t grid, uint64_t n_tiles, size_t lds_bytes) {
+                          uint32_t grid, uint64_t n_tiles, size_t lds_bytes, uint64_t wt_from = kNoWtTail) {
     t_last_launch = {t_last_launch.seq + 1, kind, cap.nt, cap.lt, acc, lds ? CEC_ENGINE_LDS : CEC_ENGINE_PERM,
-                     split_shift, flags, grid, n_tiles, lds_bytes};
+                     split_shift, flags, grid, n_tiles, lds_bytes, wt_from};
 }
 
 CEC_API int cec_last_launch(cec_launch_record *out) {
@@ -640,7 +674,7 @@ static int launch_combine(int dev, const Streams &st, const Tables &tb, const La
                           const TileSource &src, hipStream_t stream, uint32_t flags = 0, bool *released = nullptr) {
     CombineArgs a;
     memset(&a, 0, sizeof a);
-    a.flags = flags | (write_through(src.n_tiles, sh.nt + sh.lt) ? kFlagWriteThrough : 0u);
+    a.flags = flags;
     // Which kernel runs: the exact-shape one if the shape has an instantiation, the narrow
     // two-slot one for 1 x 1 launches over slots 0 and 1, else a capacity kernel.
     const bool exact_k = sh.exact && has_exact(sh.en, sh.el, sh.eacc);
@@ -660,6 +694,12 @@ static int launch_combine(int dev, const Streams &st, const Tables &tb, const La
     // persistent grid-stride grid: DESIGN.md).  The LDS engine stages its pattern's
     // product rows per workgroup (512 B for an RS(3,2) encode, from L2).
     a.split_shift = split_shift_for(st, src);
+    // The store policy.  A tail needs the full block's wt_from and the PERM engine's store
+    // branch: the narrow and the LDS engine's kernels have neither, and get no tail.
+    const StoreChoice wt = write_through(src.n_tiles, a.split_shift, sh.lt,
+                                         src.n_tiles * kTile * static_cast<uint64_t>(sh.nt + sh.lt));
+    a.wt_from = kind == kKindNarrow || lds ? kNoWtTail : wt.from;
+    a.flags |= (wt.all ? kFlagWriteThrough : 0u) | (a.wt_from != kNoWtTail ? kFlagWtTail : 0u);
     const size_t lds_bytes = std::max(lds ? static_cast<size_t>(sh.max_rows) * 256 : 0,
                                       occupancy_lds(dev, a.split_shift));
     // A dispatch holds at most 2^32 - 1 work items per dimension: past that (more than
@@ -689,7 +729,7 @@ static int launch_combine(int dev, const Streams &st, const Tables &tb, const La
                          sh.en, sh.el);
     if (released) *released = kind == kKindNarrow && (flags & kFlagSysRelease) != 0;
     record_launch(kind, cap, kind == kKindGeneric ? static_cast<int>(kAccRuntime) : sh.eacc, lds, a.split_shift,
-                  a.flags, a.grid, src.n_tiles, lds_bytes);
+                  a.flags, a.grid, src.n_tiles, lds_bytes, a.wt_from);
     return CEC_OK;
 }
 

@@ -112,7 +112,7 @@ class LaunchRecord(ctypes.Structure):
     _fields_ = [("seq", ctypes.c_uint64), ("kind", ctypes.c_int), ("nt", ctypes.c_int),
                 ("lt", ctypes.c_int), ("acc", ctypes.c_int), ("engine", ctypes.c_int),
                 ("split_shift", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("grid", ctypes.c_uint32),
-                ("n_tiles", ctypes.c_uint64), ("lds_bytes", ctypes.c_uint64)]
+                ("n_tiles", ctypes.c_uint64), ("lds_bytes", ctypes.c_uint64), ("wt_from", ctypes.c_uint64)]
 
 
 CEC_KERNEL_NARROW, CEC_KERNEL_EXACT, CEC_KERNEL_GENERIC = 0, 1, 2
@@ -129,7 +129,8 @@ class ScrubFinding(ctypes.Structure):
                 ("syndromes", ctypes.c_uint32), ("ruled_out", ctypes.c_uint32), ("lid", ctypes.c_int32)]
 
 CEC_ACC_NONE, CEC_ACC_ALL, CEC_ACC_ALL_BUT_LAST, CEC_ACC_RUNTIME = 0, 1, 2, 3
-CEC_LAUNCH_SYS_RELEASE, CEC_LAUNCH_WRITE_THROUGH = 1, 2
+CEC_LAUNCH_SYS_RELEASE, CEC_LAUNCH_WRITE_THROUGH, CEC_LAUNCH_WT_TAIL = 1, 2, 4
+CEC_NO_WT_TAIL = 2**64 - 1  # cec_launch_record.wt_from of a launch without a write-through tail
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -146,6 +147,8 @@ _SIGS = {
     "cec_last_engine": ([], _i),
     "cec_internal_check_launch_layout": ([_i, _ip, _i, _ip, _i, _pp, _i], _i),
     "cec_internal_store_policy": ([ctypes.POINTER(ctypes.c_uint64)], _i),
+    "cec_internal_wt_from": ([ctypes.c_uint64, _u32, _i, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+                              ctypes.POINTER(ctypes.c_uint64)], _i),
     "cec_internal_fail_launch": ([_i], _i),
     "cec_plan_release_stream": ([_vp, _vp], _i),
     "cec_plan_tracked_streams": ([_vp], _i),
@@ -408,6 +411,16 @@ def store_policy() -> tuple[str, int]:
     v = ctypes.c_uint64()
     p = lib().cec_internal_store_policy(ctypes.byref(v))
     return {0: "auto", 1: "nt", 2: "wt"}[p], int(v.value)
+
+
+def wt_from(n_tiles: int, split_shift: int, lt: int, streamed: int) -> tuple[str, int, int]:
+    """cec_internal_wt_from (host only): ('nt' | 'tail' | 'wt', the first write-through work
+    item or CEC_NO_WT_TAIL, the tail bytes in force) for a launch of that shape."""
+    tail, first = ctypes.c_uint64(), ctypes.c_uint64()
+    c = lib().cec_internal_wt_from(n_tiles, split_shift, lt, streamed, ctypes.byref(tail), ctypes.byref(first))
+    if c < 0:
+        _check(c)
+    return {0: "nt", 1: "tail", 2: "wt"}[c], int(first.value), int(tail.value)
 
 
 def fail_launch(after: int) -> None:

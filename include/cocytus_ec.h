@@ -626,7 +626,9 @@ enum { CEC_KERNEL_NARROW = 0, CEC_KERNEL_EXACT = 1, CEC_KERNEL_GENERIC = 2,
        CEC_KERNEL_DIGEST_CHECK = 5 /* cec_scrub_digests: nt / lt = the capacities {4,8,16} x {1,2,4},
                                     * acc = CEC_ACC_ALL, PERM, flags 0 */ };
 enum { CEC_ACC_NONE = 0, CEC_ACC_ALL = 1, CEC_ACC_ALL_BUT_LAST = 2, CEC_ACC_RUNTIME = 3 };
-enum { CEC_LAUNCH_SYS_RELEASE = 1, CEC_LAUNCH_WRITE_THROUGH = 2 };
+enum { CEC_LAUNCH_SYS_RELEASE = 1, CEC_LAUNCH_WRITE_THROUGH = 2,
+       CEC_LAUNCH_WT_TAIL = 4 /* non-temporal body, write-through stores from work item wt_from on */ };
+#define CEC_NO_WT_TAIL UINT64_MAX
 typedef struct cec_launch_record {
     uint64_t seq;           /* launches this thread has enqueued so far, this one included; never resets */
     int kind;               /* CEC_KERNEL_NARROW (two-slot 1 x 1), _EXACT (shape) or _GENERIC (capacity) */
@@ -641,6 +643,8 @@ typedef struct cec_launch_record {
     uint32_t grid;          /* workgroups */
     uint64_t n_tiles;
     uint64_t lds_bytes;     /* dynamic LDS of the launch */
+    uint64_t wt_from;       /* CEC_LAUNCH_WT_TAIL: the first work item (tile << split_shift | part) whose
+                             * stores write through; CEC_NO_WT_TAIL otherwise */
 } cec_launch_record;
 int cec_last_launch(cec_launch_record *out);
 
@@ -656,6 +660,12 @@ int cec_last_launch(cec_launch_record *out);
 int cec_internal_check_launch_layout(int narrow, const int *in_slots, int n_in, const int *out_slots,
                                      int n_out, const void *const *bases, int n_bases);
 int cec_internal_store_policy(uint64_t *wt_max_bytes);
+/* cec_internal_wt_from: the store choice of a launch of n_tiles tiles in 2^split_shift
+ * workgroups each, lt outputs, `streamed` bytes read and written: 0 non-temporal, 2
+ * write-through, 1 a non-temporal body and a write-through tail from work item *wt_from
+ * (CEC_NO_WT_TAIL otherwise).  *wt_tail_bytes: the tail in force (CEC_WT_TAIL_BYTES). */
+int cec_internal_wt_from(uint64_t n_tiles, uint32_t split_shift, int lt, uint64_t streamed,
+                         uint64_t *wt_tail_bytes, uint64_t *wt_from);
 /* cec_internal_fail_launch: fault injection for the error paths (tests only) -- the calling
  * thread's next `after` kernel launches run and the one after them fails as a HIP error
  * would (CEC_EHIP, nothing launched); then the hook disarms.  after < 0 disarms it. */
