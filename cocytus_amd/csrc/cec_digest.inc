@@ -106,9 +106,8 @@ CEC_API int cec_digest_region(int n, const uint8_t *const *arenas, uint8_t *cons
 static int digest_check_launch(int dev, cec_scrub_report *s, int k, int m, const int *matrix,
                                const uint8_t *const *data, const uint8_t *const *parity, int p0, int lt,
                                const TileSource &src, hipStream_t stream) {
-    (void)m;
     if (int rc = launch_countdown()) return rc;
-    const std::vector<Pattern> pats = scrub_patterns(k, matrix, p0, lt);
+    const std::vector<Pattern> pats = scrub_patterns(Code{k, m, matrix}, p0, lt);
     DigestCheckArgs a;
     memset(&a, 0, sizeof a);
     for (int j = 0; j < k; ++j) a.dig[j] = data[j];

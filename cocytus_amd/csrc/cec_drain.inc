@@ -90,8 +90,9 @@ int pack_threads() {
 
 struct cec_drainer {
     int device = -1;
-    int k = 0, m = 0, lid_self = 0;
+    int lid_self = 0;
     std::vector<int> matrix;
+    Code code;  // over `matrix`
     size_t half = 0;       // staging bytes per half (>= the largest update)
     size_t tile_half = 0;  // tiles per half
     uint8_t *h_stage = nullptr, *d_stage = nullptr;  // 2 x half
@@ -147,10 +148,8 @@ CEC_API int cec_drainer_create(cec_drainer **out, int k, int m, const int *matri
     cec_drainer *d = new (std::nothrow) cec_drainer;
     if (!d) return fail(CEC_ENOMEM, "cec_drainer_create: host allocation");
     d->device = dev;
-    d->k = k;
-    d->m = m;
     d->lid_self = lid_self;
-    d->matrix.assign(matrix, matrix + (k + m) * k);
+    d->code = Code::owned(d->matrix, k, m, matrix);
     d->half = (staging_bytes + 15) & ~static_cast<size_t>(15);
     d->tile_half = d->half / 16 + 1024;  // worst case: 16-byte updates, one tile each
     d->h_stage = static_cast<uint8_t *>(pin_cache().acquire(dev, 2 * d->half));
@@ -181,7 +180,7 @@ CEC_API uint8_t *cec_drainer_staging(cec_drainer *d, size_t *capacity) {
 static int drainer_check(const cec_drainer *d, const cec_host_update *u, int n, const char *op) {
     if (!d || n < 0 || (n > 0 && !u)) return fail(CEC_EINVAL, "%s: bad args", op);
     for (int i = 0; i < n; ++i) {
-        if (u[i].src_lid >= static_cast<uint32_t>(d->k) || (u[i].len && !u[i].buf))
+        if (u[i].src_lid >= static_cast<uint32_t>(d->code.k) || (u[i].len && !u[i].buf))
             return fail(CEC_EINVAL, "%s: update %d: src_lid %u / buf", op, i, u[i].src_lid);
         if (u[i].len > d->half)
             return fail(CEC_EINVAL, "%s: update %d (%u B) exceeds staging", op, i, u[i].len);
@@ -203,13 +202,15 @@ static int drain_bail(hipStream_t s, int rc) {
 }
 
 // The fold launches of one round, one per overlap wave: `spans` are the waves' tile ranges
-// in the round's tile list (dt on the device, ht the same tiles on the host).
-static int drainer_fold(cec_drainer *d, int dev, const Streams &st, const std::vector<Combo> &combos, const Tile *dt,
+// in the round's tile list (dt on the device, ht the same tiles on the host).  `stage`: the
+// device address the tiles' src_off count from.
+static int drainer_fold(cec_drainer *d, int dev, const uint8_t *stage, uint8_t *parity, const Tile *dt,
                         const Tile *ht, const std::vector<std::pair<size_t, size_t>> &spans, hipStream_t s) {
+    const Fold f = fold(d->code, d->lid_self, stage, parity);  // pattern j = source shard j
     for (const auto &sp : spans) {
         if (sp.second == sp.first) continue;
         const TileSource wave = TileSource::window(dt + sp.first, ht + sp.first, sp.second - sp.first);
-        if (int r = run_combos(dev, st, combos, wave, s)) return drain_bail(s, r);
+        if (int r = run_combos(dev, f.st, f.combos, wave, s)) return drain_bail(s, r);
         ++d->last_launches;
     }
     return CEC_OK;
@@ -220,11 +221,7 @@ static int drainer_fold(cec_drainer *d, int dev, const Streams &st, const std::v
 // rounds of the tile buffer's capacity).
 static int drainer_apply_in_place(cec_drainer *d, const cec_host_update *u,
                                   const std::vector<int> &order, const std::vector<int> &wave,
-                                  const std::vector<Combo> &combos, uint8_t *parity, int dev,
-                                  hipStream_t s) {
-    Streams st;
-    st.base[0] = d->d_stage;
-    st.base[1] = parity;
+                                  uint8_t *parity, int dev, hipStream_t s) {
     const size_t tcap = 2 * d->tile_half;
     size_t next = 0;
     while (next < order.size()) {
@@ -245,7 +242,7 @@ static int drainer_apply_in_place(cec_drainer *d, const cec_host_update *u,
             ++next;
         }
         HIP_TRY(hipMemcpyAsync(d->d_tiles, d->h_tiles, nt * sizeof(Tile), hipMemcpyHostToDevice, s));
-        if (int r = drainer_fold(d, dev, st, combos, d->d_tiles, d->h_tiles, spans, s)) return r;
+        if (int r = drainer_fold(d, dev, d->d_stage, parity, d->d_tiles, d->h_tiles, spans, s)) return r;
         HIP_TRY(hipStreamSynchronize(s));  // the pinned tile list is reused by the next round
     }
     return CEC_OK;
@@ -257,8 +254,7 @@ static int drainer_apply_in_place(cec_drainer *d, const cec_host_update *u,
 // host memory (a registered ecmem).  Against the pack-thread path it saves the threads'
 // wake-up, two uploads and a hipStreamSynchronize: ~15 us instead of ~45-60 per window.
 static int drainer_apply_small(cec_drainer *d, const cec_host_update *u, const std::vector<int> &order,
-                               const std::vector<int> &wave, const std::vector<Combo> &combos, uint8_t *parity,
-                               int dev, hipStream_t s) {
+                               const std::vector<int> &wave, uint8_t *parity, int dev, hipStream_t s) {
     if (!d->sm_h) {
         d->sm_h = static_cast<uint8_t *>(map_cache().acquire(dev, kDrainSmallBytes));
         d->smt_h = static_cast<Tile *>(map_cache().acquire(dev, kDrainSmallTiles * sizeof(Tile)));
@@ -287,10 +283,7 @@ static int drainer_apply_small(cec_drainer *d, const cec_host_update *u, const s
         spans.back().second = nt;
         so += (x.len + 15) & ~static_cast<size_t>(15);
     }
-    Streams st;
-    st.base[0] = d->sm_d;
-    st.base[1] = parity;
-    if (int r = drainer_fold(d, dev, st, combos, d->smt_d, d->smt_h, spans, s)) return r;
+    if (int r = drainer_fold(d, dev, d->sm_d, parity, d->smt_d, d->smt_h, spans, s)) return r;
     hipPointerAttribute_t at;  // the arena in host memory (registered): fence the results
     bool host = true;
     if (hipPointerGetAttributes(&at, parity) == hipSuccess)
@@ -409,25 +402,12 @@ CEC_API int cec_drainer_apply(cec_drainer *d, const cec_host_update *u, int n, u
     }
     std::vector<int> wave;
     const int n_waves = overlap_waves(u, n, wave);
-    const int k = d->k;
-    const int *matrix = d->matrix.data();
-    std::vector<Combo> combos(k);  // pattern j = source shard j
-    for (int j = 0; j < k; ++j) {
-        combos[j].n_in = 1;
-        combos[j].in_stream[0] = 0;
-        combos[j].in_src[0] = 1;
-        Combo::Out o{};
-        o.stream = 1;
-        o.mode = kModeXor;
-        o.coef[0] = MATRIX(d->lid_self, j);
-        combos[j].outs.push_back(o);
-    }
     std::vector<int> order(n);
     for (int i = 0; i < n; ++i) order[i] = i;
     if (n_waves > 1)
         std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return wave[a] < wave[b]; });
 
-    if (in_place) return drainer_apply_in_place(d, u, order, wave, combos, parity, dev, s);
+    if (in_place) return drainer_apply_in_place(d, u, order, wave, parity, dev, s);
     {
         size_t bytes = 0, tiles = 0;
         for (int i = 0; i < n && bytes <= kDrainSmallBytes && tiles <= kDrainSmallTiles; ++i) {
@@ -435,7 +415,7 @@ CEC_API int cec_drainer_apply(cec_drainer *d, const cec_host_update *u, int n, u
             tiles += tiles_of(u[i].addr, u[i].len);
         }
         if (bytes <= kDrainSmallBytes && tiles <= kDrainSmallTiles)
-            return drainer_apply_small(d, u, order, wave, combos, parity, dev, s);
+            return drainer_apply_small(d, u, order, wave, parity, dev, s);
     }
 
     struct Item {
@@ -495,10 +475,8 @@ CEC_API int cec_drainer_apply(cec_drainer *d, const cec_host_update *u, int n, u
                                hipMemcpyHostToDevice, s));
         HIP_TRY(hipEventRecord(d->ev[h], s));  // pinned half h reusable once this fires
         d->pending[h] = true;
-        Streams st;
-        st.base[0] = d->d_stage;  // tiles carry src_off relative to the whole staging area
-        st.base[1] = parity;
-        if (int r = drainer_fold(d, dev, st, combos, d->d_tiles + h * d->tile_half, ht, spans, s)) {
+        // (tiles carry src_off relative to the whole staging area)
+        if (int r = drainer_fold(d, dev, d->d_stage, parity, d->d_tiles + h * d->tile_half, ht, spans, s)) {
             d->pending[0] = d->pending[1] = false;
             return r;
         }

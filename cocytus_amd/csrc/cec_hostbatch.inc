@@ -319,6 +319,14 @@ struct HostBatchCtx {  // per thread and device
 };
 thread_local HostBatchCtx t_hb;
 
+// The streams of one round, the same slots in every round (the patterns are built once per
+// batch): D, addressed by tile.off; S; B.
+struct HbStreams {
+    Streams st;
+    int d, s, b;
+    HbStreams(uint8_t *D, uint8_t *S, uint8_t *B) : d(st.add(D)), s(st.add(S)), b(st.add(B)) {}
+};
+
 inline bool ranges_meet(uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a < b + nb && b < a + na; }
 
 }  // namespace
@@ -416,48 +424,28 @@ CEC_API int cec_region_multiply_batch(const cec_region_job *jobs, int n, void *s
         }
     }
     for (HbCluster &c : cl) c.waves = hb_cluster_waves(pc, ids.data() + c.first, c.count, &c.packed);
-    // patterns: one per distinct (kind, multby)
+    // patterns: one per distinct (kind, multby) of the batch, in key order (the table set is
+    // cached by content).  combos_ip: the same patterns for rounds that read their bases in
+    // place: S by tile.off (it mirrors D), B by tile.src_off (the base's offset in its
+    // registered region)
+    const HbStreams slots(nullptr, nullptr, nullptr);  // (the slots alone)
+    auto hb_combo = [&](int kind, int multby, bool in_place) {
+        Combo cb;
+        Combo::Out &o = cb.out(slots.d, kind == kHbXor ? kModeXor : kModeWrite);
+        o.coef[cb.in(slots.s, !in_place)] = multby;
+        if (kind == kHbBase) o.coef[cb.in(slots.b, true)] = 1;
+        return cb;
+    };
     std::vector<int> pat_of(3 * 256, -1);
-    std::vector<Combo> combos;
-    for (HbPiece &p : pc) {
-        int &slot = pat_of[p.kind * 256 + p.multby];
-        if (slot < 0) {
-            Combo cb;
-            cb.n_in = p.kind == kHbBase ? 2 : 1;
-            cb.in_stream[0] = 1;  // S
-            cb.in_src[0] = 1;
-            cb.in_stream[1] = 2;  // B
-            cb.in_src[1] = 1;
-            Combo::Out o{};
-            o.stream = 0;  // D
-            o.src = 0;
-            o.mode = p.kind == kHbXor ? kModeXor : kModeWrite;
-            o.coef[0] = p.multby;
-            o.coef[1] = 1;
-            cb.outs.push_back(o);
-            slot = static_cast<int>(combos.size());
-            combos.push_back(cb);
-        }
-        p.pat = slot;
+    for (const HbPiece &p : pc) pat_of[p.kind * 256 + p.multby] = 0;
+    std::vector<Combo> combos, combos_ip;
+    for (int key = 0; key < 3 * 256; ++key) {
+        if (pat_of[key] < 0) continue;
+        pat_of[key] = static_cast<int>(combos.size());
+        combos.push_back(hb_combo(key >> 8, key & 255, false));
+        combos_ip.push_back(hb_combo(key >> 8, key & 255, true));
     }
-    // a deterministic pattern order (the table set is cached by content)
-    {
-        std::vector<int> keys;
-        for (int key = 0; key < 3 * 256; ++key)
-            if (pat_of[key] >= 0) keys.push_back(key);
-        std::vector<int> remap(combos.size());
-        std::vector<Combo> sorted;
-        for (int key : keys) {
-            remap[pat_of[key]] = static_cast<int>(sorted.size());
-            sorted.push_back(combos[pat_of[key]]);
-        }
-        combos.swap(sorted);
-        for (HbPiece &p : pc) p.pat = remap[p.pat];
-    }
-    // the same patterns for rounds that read their bases in place: S by tile.off (it mirrors
-    // D), B by tile.src_off (the base's offset in its registered region)
-    std::vector<Combo> combos_ip = combos;
-    for (Combo &c : combos_ip) c.in_src[0] = 0;
+    for (HbPiece &p : pc) p.pat = pat_of[p.kind * 256 + p.multby];
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (stream_capturing(s))  // a synchronous call: it waits for its own launches
         return fail(CEC_EINVAL, "cec_region_multiply_batch: the stream is being captured into a graph");
@@ -604,15 +592,13 @@ CEC_API int cec_region_multiply_batch(const cec_region_job *jobs, int n, void *s
         const clk::time_point t0 = clk::now();
         hb_copy(hb.pool.get(), in);
         hb.t_pack += us(t0, clk::now());
-        Streams st;
-        st.base[0] = stage_dev;             // D (addressed by tile.off)
-        st.base[1] = stage_dev + rd.dseg;   // S (by tile.src_off; in place: by tile.off)
-        st.base[2] = rd.in_place ? rd.reg.alias                                          // B in place
-                                 : rd.any_base ? stage_dev + rd.dseg + rd.sseg : stage_dev + rd.dseg;  // B staged
+        const HbStreams hs(stage_dev, stage_dev + rd.dseg,  // D; S (by tile.src_off; in place: by tile.off)
+                           rd.in_place ? rd.reg.alias       // B in place
+                                       : rd.any_base ? stage_dev + rd.dseg + rd.sseg : stage_dev + rd.dseg);  // B staged
         for (int w = 0; w < max_wave; ++w) {
             if (span[w + 1] == span[w]) continue;
             const TileSource wave = TileSource::window(dt + span[w], ht + span[w], span[w + 1] - span[w]);
-            if (int r = run_combos(dev, st, rd.in_place ? combos_ip : combos, wave, s)) return r;
+            if (int r = run_combos(dev, hs.st, rd.in_place ? combos_ip : combos, wave, s)) return r;
             ++hb.last_launches;
             hb.last_in_place += rd.in_place;
         }

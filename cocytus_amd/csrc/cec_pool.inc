@@ -98,8 +98,9 @@ struct PoolTables {
 
 struct cec_recovery_pool {
     int device = -1;
-    int k = 0, m = 0, lid_self = 0;
+    int lid_self = 0;
     std::vector<int> matrix;
+    Code code;  // over `matrix`
     const uint8_t *parity = nullptr;  // this parity's arena (device)
     int capacity = 0;                 // units
     uint8_t *residual = nullptr;      // device, capacity * kTile
@@ -170,10 +171,8 @@ CEC_API int cec_recovery_pool_create(cec_recovery_pool **out, int k, int m, cons
     cec_recovery_pool *p = new (std::nothrow) cec_recovery_pool;
     if (!p) return fail(CEC_ENOMEM, "cec_recovery_pool_create: host allocation");
     p->device = dev;
-    p->k = k;
-    p->m = m;
     p->lid_self = lid_self;
-    p->matrix.assign(matrix, matrix + (k + m) * k);
+    p->code = Code::owned(p->matrix, k, m, matrix);
     p->parity = parity_arena;
     p->capacity = capacity_units;
     const size_t bytes = static_cast<size_t>(capacity_units) * kTile;
@@ -199,7 +198,7 @@ CEC_API int cec_recovery_pool_create(cec_recovery_pool **out, int k, int m, cons
 
 CEC_API int cec_recovery_pool_begin(cec_recovery_pool *p, uint32_t mask, int unit_begin, int unit_end) {
     if (!p || unit_begin < 0 || unit_end < unit_begin || !(mask & (1u << p->lid_self)) ||
-        !mask_ok(p->k, p->m, mask))
+        !mask_ok(p->code.k, p->code.m, mask))
         return fail(CEC_EINVAL, "cec_recovery_pool_begin: bad mask 0x%x / units [%d, %d]", mask, unit_begin,
                     unit_end);
     const int n = unit_end - unit_begin + 1;
@@ -246,7 +245,7 @@ static cec_recovery_pool::Req *pool_req(cec_recovery_pool *p, int id) {
 
 CEC_API int cec_recovery_pool_add_peer(cec_recovery_pool *p, int id, int peer, const void *units) {
     cec_recovery_pool::Req *r = pool_req(p, id);
-    if (!r || !units || peer < 0 || peer >= p->k || !(r->mask & (1u << peer)))
+    if (!r || !units || peer < 0 || peer >= p->code.k || !(r->mask & (1u << peer)))
         return fail(CEC_EINVAL, "cec_recovery_pool_add_peer: request %d / peer %d", id, peer);
     if (r->contributed & (1u << peer))
         return fail(CEC_EINVAL, "cec_recovery_pool_add_peer: peer %d already applied (recovery.c:75)", peer);
@@ -281,7 +280,7 @@ CEC_API int cec_recovery_pool_add_peers(cec_recovery_pool *p, const int *ids, co
     for (int i = 0; i < n; ++i) {
         const cec_recovery_pool::Req *r = pool_req(p, ids[i]);
         const int peer = peers[i];
-        if (!r || !units[i] || peer < 0 || peer >= p->k || !(r->mask & (1u << peer)))
+        if (!r || !units[i] || peer < 0 || peer >= p->code.k || !(r->mask & (1u << peer)))
             return fail(CEC_EINVAL, "cec_recovery_pool_add_peers: reply %d: request %d / peer %d", i, ids[i], peer);
         if (r->contributed & (1u << peer))
             return fail(CEC_EINVAL, "cec_recovery_pool_add_peers: reply %d: peer %d already applied (recovery.c:75)",
@@ -298,7 +297,7 @@ CEC_API int cec_recovery_pool_add_peers(cec_recovery_pool *p, const int *ids, co
 
 CEC_API uint8_t *cec_recovery_pool_staging(cec_recovery_pool *p, int id, int peer, size_t *len) {
     cec_recovery_pool::Req *r = pool_req(p, id);
-    if (!r || peer < 0 || peer >= p->k) return nullptr;
+    if (!r || peer < 0 || peer >= p->code.k) return nullptr;
     if (len) *len = static_cast<size_t>(r->nunits) * kTile;
     return p->q_host[peer] + static_cast<size_t>(r->slot) * kTile;
 }
@@ -321,6 +320,43 @@ static int pool_out_host(cec_recovery_pool *p) {  // the _host solves' output, o
     return CEC_OK;
 }
 
+// The streams of a flush.  Its patterns outlive the call (PoolTables is append-only), so the
+// slots are a function of k alone, the same in every flush: P, R, the k reply stagings, the
+// k arenas of a flush_solve (empty without `out`), out_host (empty unless to_host).
+struct FlushStreams {
+    Streams st;
+    int parity, residual, q[CEC_MAX_K], out[CEC_MAX_K], out_host;
+    FlushStreams(const cec_recovery_pool *p, uint8_t *const *o, bool to_host)
+        : parity(st.add(p->parity)), residual(st.add(p->residual)) {
+        for (int j = 0; j < p->code.k; ++j) q[j] = st.add(p->q_dev[j]);
+        for (int j = 0; j < p->code.k; ++j) out[j] = st.add(o ? o[j] : nullptr);
+        out_host = st.add(to_host ? p->out_dev : nullptr);
+    }
+};
+
+// A single loss led by parity lid_self (the pool solves no other): its lost data lid, else -1.
+static int pool_single_loss(const cec_recovery_pool *p, uint32_t mask) {
+    Loss ls;
+    if (Loss::of(p->code, mask, "recovery pool", &ls, false) || ls.n != 1 || ls.pars[0] != p->lid_self) return -1;
+    return ls.lost[0];
+}
+
+// The pool's mapped diff staging, grown to hold `len` bytes (idle: every earlier call
+// completed before returning).
+static int pool_diff_staging(cec_recovery_pool *p, size_t len, const char *op) {
+    if (p->diff_cap >= len) return CEC_OK;
+    map_cache().release(p->device, p->diff_host, p->diff_cap);
+    p->diff_host = p->diff_dev = nullptr;
+    p->diff_cap = std::max<size_t>(len, size_t(1) << 20);
+    p->diff_host = static_cast<uint8_t *>(map_cache().acquire(p->device, p->diff_cap));
+    if (!p->diff_host) {
+        p->diff_cap = 0;
+        return fail(CEC_ENOMEM, "%s: %zu bytes of diff staging", op, len);
+    }
+    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&p->diff_dev), p->diff_host, 0));
+    return CEC_OK;
+}
+
 // to_host: the solves go to out_host at the request's slots instead of out[lost].
 static int pool_flush(cec_recovery_pool *p, uint8_t *const *out, bool to_host, void *stream, int *solved) {
     if (solved) *solved = 0;
@@ -333,8 +369,8 @@ static int pool_flush(cec_recovery_pool *p, uint8_t *const *out, bool to_host, v
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     UseNote note_{p->uses, s};
-    const int k = p->k, m = p->m;
-    const int *matrix = p->matrix.data();
+    const int k = p->code.k;
+    const FlushStreams fs(p, out, to_host);
     const int engine = op_engine(false);
     if (p->tables.engine != engine) {  // the table's coefficient form is per engine
         p->tables.reset(dev, engine);
@@ -349,9 +385,8 @@ static int pool_flush(cec_recovery_pool *p, uint8_t *const *out, bool to_host, v
         cec_recovery_pool::Req &r = p->reqs[id];
         int lost = -1;
         if ((out || to_host) && cec_recovery_pool_complete(p, id)) {
-            int lo[CEC_MAX_K], pa[CEC_MAX_M];
-            if (mask_split(k, m, r.mask, lo, pa) == 1 && pa[0] == p->lid_self && (to_host || out[lo[0]]))
-                lost = lo[0];
+            lost = pool_single_loss(p, r.mask);
+            if (lost >= 0 && !to_host && !out[lost]) lost = -1;
         }
         const uint64_t key = r.queued | (r.touch_pending ? 1ull << 31 : 0ull) |
                              (static_cast<uint64_t>(lost + 1) << 32) |
@@ -359,35 +394,16 @@ static int pool_flush(cec_recovery_pool *p, uint8_t *const *out, bool to_host, v
         auto it = p->flush_pat.find(key);
         if (it == p->flush_pat.end()) {
             Combo c;
-            Combo::Out o{};
-            o.stream = 1;     // R, slot-addressed
-            o.src = 1;
-            o.mode = kModeWrite;
-            if (r.touch_pending) {
-                c.in_stream[c.n_in] = 0;  // P, arena-addressed: the first-touch copy (recovery.c:79-82)
-            } else {
-                c.in_stream[c.n_in] = 1;  // R itself
-                c.in_src[c.n_in] = 1;
-            }
-            o.coef[c.n_in++] = 1;
+            Combo::Out &o = c.out(fs.residual, kModeWrite, true);  // R, slot-addressed
+            // P, arena-addressed: the first-touch copy (recovery.c:79-82); else R itself
+            o.coef[r.touch_pending ? c.in(fs.parity) : c.in(fs.residual, true)] = 1;
             for (int j = 0; j < k; ++j)
-                if (r.queued & (1u << j)) {
-                    c.in_stream[c.n_in] = static_cast<uint8_t>(2 + j);
-                    c.in_src[c.n_in] = 1;
-                    o.coef[c.n_in++] = MATRIX(p->lid_self, j);  // recovery.c:91-93
-                }
-            c.outs.push_back(o);
+                if (r.queued & (1u << j)) o.coef[c.in(fs.q[j], true)] = p->code.at(p->lid_self, j);  // recovery.c:91-93
             if (lost >= 0) {  // the leader's bottom half in the same pass (memcached.c:7907-7922)
-                const int inv = gf_inv(MATRIX(p->lid_self, lost));
-                Combo::Out q{};
-                q.stream = static_cast<uint8_t>(2 + k + lost);  // lost lid's arena, arena offset
-                if (to_host) {
-                    q.stream = static_cast<uint8_t>(2 + k);  // out_host, slot-addressed
-                    q.src = 1;
-                }
-                q.mode = kModeWrite;
-                for (int i = 0; i < c.n_in; ++i) q.coef[i] = gf_mul(inv, o.coef[i]);
-                c.outs.push_back(q);
+                const int inv = gf_inv(p->code.at(p->lid_self, lost));
+                // the lost lid's arena, arena offset; or out_host, slot-addressed
+                Combo::Out &q = to_host ? c.out(fs.out_host, kModeWrite, true) : c.out(fs.out[lost], kModeWrite);
+                for (int i = 0; i < c.n_in; ++i) q.coef[i] = gf_mul(inv, c.outs[0].coef[i]);
             }
             // (<= 2 outputs: one pattern; refused before the table or the key map change)
             const int at = static_cast<int>(p->tables.pats.size());
@@ -407,16 +423,8 @@ static int pool_flush(cec_recovery_pool *p, uint8_t *const *out, bool to_host, v
     }
     used.resize(p->tables.pats.size(), 0);
     if (int rc = p->tables.sync(s)) return rc;
-    Streams st;
-    st.base[0] = const_cast<uint8_t *>(p->parity);
-    st.base[1] = p->residual;
-    for (int j = 0; j < k; ++j) {
-        st.base[2 + j] = p->q_dev[j];
-        if (out) st.base[2 + k + j] = out[j];
-    }
-    if (to_host) st.base[2 + k] = p->out_dev;
     // (the pool's tile buffer: whole 4 KiB units on 4 KiB offsets)
-    if (int rc = launch_combine(dev, st, Tables{p->tables.d, p->tables.cap_pats, p->tables.pats.data(), &used},
+    if (int rc = launch_combine(dev, fs.st, Tables{p->tables.d, p->tables.cap_pats, p->tables.pats.data(), &used},
                                 launch_shape(p->tables.pats, &used), engine == CEC_ENGINE_LDS,
                                 TileSource::whole_units(p->d_tiles, nt), s))
         return rc;
@@ -468,13 +476,13 @@ CEC_API int cec_recovery_pool_solved(const cec_recovery_pool *p, int id) {
 CEC_API int cec_recovery_pool_complete(const cec_recovery_pool *p, int id) {
     if (!p || id < 0 || id >= static_cast<int>(p->reqs.size()) || !p->reqs[id].used) return 0;
     const cec_recovery_pool::Req &r = p->reqs[id];
-    const uint32_t data = r.mask & ((1u << p->k) - 1);
+    const uint32_t data = r.mask & ((1u << p->code.k) - 1);
     return (r.contributed & data) == data ? 1 : 0;
 }
 
 CEC_API int cec_recovery_pool_fold_update(cec_recovery_pool *p, int peer, uint64_t addr, const void *diff,
                                           uint32_t len, void *stream) {
-    if (!p || (len && !diff) || peer < 0 || peer >= p->k)
+    if (!p || (len && !diff) || peer < 0 || peer >= p->code.k)
         return fail(CEC_EINVAL, "cec_recovery_pool_fold_update: bad args");
     if (len == 0) return 0;
     int dev;
@@ -503,35 +511,12 @@ CEC_API int cec_recovery_pool_fold_update(cec_recovery_pool *p, int peer, uint64
     if (nt == 0) return 0;
     const uint8_t *d = static_cast<const uint8_t *>(device_view_of(diff));
     if (!d) {  // pageable diff: through the pool's mapped pinned staging (zero-copy)
-        if (p->diff_cap < len) {  // (idle: every earlier call completed before returning)
-            map_cache().release(p->device, p->diff_host, p->diff_cap);
-            p->diff_host = p->diff_dev = nullptr;
-            p->diff_cap = std::max<size_t>(len, size_t(1) << 20);
-            p->diff_host = static_cast<uint8_t *>(map_cache().acquire(p->device, p->diff_cap));
-            if (!p->diff_host) {
-                p->diff_cap = 0;
-                return fail(CEC_ENOMEM, "cec_recovery_pool_fold_update: %u bytes of diff staging", len);
-            }
-            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&p->diff_dev), p->diff_host, 0));
-        }
+        if (int rc = pool_diff_staging(p, len, "cec_recovery_pool_fold_update")) return rc;
         memcpy(p->diff_host, diff, len);
         d = p->diff_dev;
     }
-    const int k = p->k;
-    const int *matrix = p->matrix.data();
-    Streams st;
-    st.base[0] = const_cast<uint8_t *>(d);
-    st.base[1] = p->residual;
-    Combo c;
-    c.n_in = 1;
-    c.in_stream[0] = 0;
-    c.in_src[0] = 1;
-    Combo::Out o{};
-    o.stream = 1;
-    o.mode = kModeXor;
-    o.coef[0] = MATRIX(p->lid_self, peer);  // recovery.c:123
-    c.outs.push_back(o);
-    if (int rc = run_combos(dev, st, {c}, TileSource::window(p->d_tiles, p->h_tiles, nt), s)) return rc;
+    const Fold f = fold(p->code, p->lid_self, d, p->residual, peer);  // recovery.c:123
+    if (int rc = run_combos(dev, f.st, f.combos, TileSource::window(p->d_tiles, p->h_tiles, nt), s)) return rc;
     if (int rc = stream_wait(s, false)) return rc;  // (the residual is in HBM)
     return units;
 }
@@ -547,7 +532,7 @@ CEC_API int cec_recovery_pool_fold_updates(cec_recovery_pool *p, const cec_host_
                                            void *stream) {
     if (!p || n < 0 || (n > 0 && !u)) return fail(CEC_EINVAL, "cec_recovery_pool_fold_updates: bad args");
     for (int i = 0; i < n; ++i)
-        if (u[i].src_lid >= static_cast<uint32_t>(p->k) || (u[i].len && !u[i].buf))
+        if (u[i].src_lid >= static_cast<uint32_t>(p->code.k) || (u[i].len && !u[i].buf))
             return fail(CEC_EINVAL, "cec_recovery_pool_fold_updates: update %d (lid %u)", i, u[i].src_lid);
     if (units)
         for (int i = 0; i < n; ++i) units[i] = 0;
@@ -604,17 +589,7 @@ CEC_API int cec_recovery_pool_fold_updates(cec_recovery_pool *p, const cec_host_
         }
     }
     if (pieces.empty()) return 0;
-    if (p->diff_cap < staged) {  // (idle: every earlier call completed before returning)
-        map_cache().release(p->device, p->diff_host, p->diff_cap);
-        p->diff_host = p->diff_dev = nullptr;
-        p->diff_cap = std::max<size_t>(staged, size_t(1) << 20);
-        p->diff_host = static_cast<uint8_t *>(map_cache().acquire(p->device, p->diff_cap));
-        if (!p->diff_host) {
-            p->diff_cap = 0;
-            return fail(CEC_ENOMEM, "cec_recovery_pool_fold_updates: %zu bytes of diff staging", staged);
-        }
-        HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&p->diff_dev), p->diff_host, 0));
-    }
+    if (int rc = pool_diff_staging(p, staged, "cec_recovery_pool_fold_updates")) return rc;
     // tiles (one per unit piece: R offsets are unit-aligned per slot), packed pieces
     std::vector<Tile> tiles;
     tiles.reserve(pieces.size() + staged / kTile + 1);
@@ -659,29 +634,14 @@ CEC_API int cec_recovery_pool_fold_updates(cec_recovery_pool *p, const cec_host_
         std::vector<size_t> fill(wave_start.begin(), wave_start.end() - 1);
         for (size_t t = 0; t < nt; ++t) h[fill[wave_of[t]]++] = tiles[t];
     }
-    const int k = p->k;
-    const int *matrix = p->matrix.data();
-    std::vector<Combo> combos(k);  // pattern index = the update's data lid
-    std::vector<char> used(k, 0);
+    // the packed diff pieces into R; pattern index = the update's data lid (recovery.c:123)
+    const Fold f = fold(p->code, p->lid_self, p->diff_dev, p->residual);
+    std::vector<char> used(p->code.k, 0);
     for (const Piece &pc : pieces) used[u[pc.upd].src_lid] = 1;
-    for (int j = 0; j < k; ++j) {
-        Combo &c = combos[j];
-        c.n_in = 1;
-        c.in_stream[0] = 0;
-        c.in_src[0] = 1;  // the packed diff pieces
-        Combo::Out o{};
-        o.stream = 1;  // R
-        o.mode = kModeXor;
-        o.coef[0] = MATRIX(p->lid_self, j);  // recovery.c:123
-        c.outs.push_back(o);
-    }
-    Streams st;
-    st.base[0] = p->diff_dev;
-    st.base[1] = p->residual;
     int rc = CEC_OK;
     for (size_t w = 0; w < nw && !rc; ++w) {
         const size_t lo = wave_start[w], n_wave = wave_start[w + 1] - lo;
-        rc = run_combos(dev, st, combos, TileSource::window(d + lo, h + lo, n_wave), s, &used);
+        rc = run_combos(dev, f.st, f.combos, TileSource::window(d + lo, h + lo, n_wave), s, &used);
     }
     if (!rc) rc = stream_wait(s, false);  // (the residual is in HBM; staging and tiles reusable)
     if (rc) {  // an earlier wave may still read the diff staging and the tiles (the pool's own
@@ -708,35 +668,22 @@ static int pool_solve(cec_recovery_pool *p, const int *ids, int n, uint8_t *cons
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     UseNote note_{p->uses, s};
-    const int k = p->k, m = p->m;
-    const int *matrix = p->matrix.data();
+    const int k = p->code.k;
     // One pattern per lost data lid x, always all k of them (out[x] = inv * R, pattern
     // index = x): one table per pool and engine in the coefficient cache, whatever the
     // mix of requests (`used` picks the kernel shape).
+    Streams st;
+    const int s_residual = st.add(p->residual), s_out_host = to_host ? st.add(p->out_dev) : -1;
     std::vector<Combo> combos(k);
     std::vector<char> used(k, 0);
     for (int x = 0; x < k; ++x) {
         Combo &c = combos[x];
-        c.n_in = 1;
-        c.in_stream[0] = 0;
-        c.in_src[0] = 1;  // R, slot-addressed
-        Combo::Out o{};
-        o.stream = static_cast<uint8_t>(1 + x);  // the lost lid's arena, arena offset
-        if (to_host) {
-            o.stream = 1;  // out_host, slot-addressed
-            o.src = 1;
-        }
-        o.mode = kModeWrite;
-        const int cx = MATRIX(p->lid_self, x);
-        o.coef[0] = cx ? gf_inv(cx) : 0;  // memcached.c:7907-7922, n_lost = 1
-        c.outs.push_back(o);
+        const int in_r = c.in(s_residual, true);  // R, slot-addressed
+        // out_host, slot-addressed; or the lost lid's arena, arena offset
+        Combo::Out &o = to_host ? c.out(s_out_host, kModeWrite, true) : c.out(st.add(out[x]), kModeWrite);
+        const int cx = p->code.at(p->lid_self, x);
+        o.coef[in_r] = cx ? gf_inv(cx) : 0;  // memcached.c:7907-7922, n_lost = 1
     }
-    Streams st;
-    st.base[0] = p->residual;
-    if (to_host)
-        st.base[1] = p->out_dev;
-    else
-        for (int j = 0; j < k; ++j) st.base[1 + j] = out[j];
     size_t nt = 0;
     std::vector<char> listed(p->reqs.size(), 0);
     for (int x = 0; x < n; ++x) {
@@ -744,21 +691,21 @@ static int pool_solve(cec_recovery_pool *p, const int *ids, int n, uint8_t *cons
         if (!r || !cec_recovery_pool_complete(p, ids[x]))
             return fail(CEC_EINVAL, "cec_recovery_pool_solve: request %d missing or incomplete", ids[x]);
         if (listed[ids[x]]++) return fail(CEC_EINVAL, "cec_recovery_pool_solve: request %d listed twice", ids[x]);
-        int lost[CEC_MAX_K], pars[CEC_MAX_M];
-        if (mask_split(k, m, r->mask, lost, pars) != 1 || pars[0] != p->lid_self)
+        const int lost = pool_single_loss(p, r->mask);
+        if (lost < 0)
             return fail(CEC_EINVAL, "cec_recovery_pool_solve: request %d is not a single-loss request "
                                     "led by this parity (use cec_recovery sessions)", ids[x]);
-        if (!to_host && !out[lost[0]]) return fail(CEC_EINVAL, "cec_recovery_pool_solve: out[%d] is NULL", lost[0]);
-        used[lost[0]] = 1;
+        if (!to_host && !out[lost]) return fail(CEC_EINVAL, "cec_recovery_pool_solve: out[%d] is NULL", lost);
+        used[lost] = 1;
         if (nt + r->nunits > static_cast<size_t>(p->capacity))  // (cannot happen once ids are distinct)
             return fail(CEC_EINVAL, "cec_recovery_pool_solve: more units than the tile buffer");
         nt += append_tiles(p->h_tiles + nt, static_cast<uint64_t>(r->ub) * kTile,
                            static_cast<uint64_t>(r->slot) * kTile, static_cast<uint32_t>(r->nunits) * kTile,
-                           static_cast<uint32_t>(lost[0]));
+                           static_cast<uint32_t>(lost));
     }
     // (whole 4 KiB units on 4 KiB offsets, as the flush's)
     if (int rc = run_combos(dev, st, combos, TileSource::whole_units(p->d_tiles, nt), s, &used)) return rc;
-    if (int rc = stream_wait(s, to_host || any_host_memory(out, p->k))) return rc;
+    if (int rc = stream_wait(s, to_host || any_host_memory(out, p->code.k))) return rc;
     for (int x = 0; x < n; ++x) {
         p->reqs[ids[x]].solved = true;
         p->reqs[ids[x]].solved_host = to_host;

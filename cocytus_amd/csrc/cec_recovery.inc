@@ -7,7 +7,7 @@
 // in HBM; every byte of arithmetic is a combine-kernel launch over the range:
 //   add_peer (recovery_recover_units, recovery.c:61-96): first peer
 //       R = P[range] ^ c*D   (first-touch copy of the parity units fused in),
-//     later peers R ^= c*D, c = MATRIX(self, peer);
+//     later peers R ^= c*D, c = M[self][peer];
 //   fold_update (recovery_try_update_unit, recovery.c:99-131): R[piece] ^= c*diff
 //     while the range is touched and the peer has not contributed;
 //   solve (complete_recovery_bottom_half, memcached.c:7842-7922): out = inv * C.
@@ -141,8 +141,9 @@ bool any_host_memory(uint8_t *const *out, int n) {
 
 struct cec_recovery {
     int device = -1;
-    int k = 0, m = 0, lid_self = 0;
+    int lid_self = 0;
     std::vector<int> matrix;
+    Code code;  // over `matrix`
     uint32_t mask = 0;
     int ub = 0, ue = 0;
     uint64_t base = 0, nbuf = 0;   // arena offset and bytes of the unit range
@@ -187,10 +188,8 @@ CEC_API int cec_recovery_create(cec_recovery **out, int k, int m, const int *mat
     cec_recovery *s = new (std::nothrow) cec_recovery;
     if (!s) return fail(CEC_ENOMEM, "cec_recovery_create: host allocation");
     s->device = dev;
-    s->k = k;
-    s->m = m;
     s->lid_self = lid_self;
-    s->matrix.assign(matrix, matrix + (k + m) * k);
+    s->code = Code::owned(s->matrix, k, m, matrix);
     s->mask = mask;
     s->ub = unit_begin;
     s->ue = unit_end;
@@ -224,8 +223,39 @@ static int device_input(cec_recovery *r, const void *p, size_t len, uint8_t *scr
     return r->stager.upload(scratch, static_cast<const uint8_t *>(p), len, s);
 }
 
+// Device scratch of `bytes` per buffer for one synchronous call, released to dev_cache()
+// when the call returns -- after a stream sync, if any was taken: work enqueued on s may
+// still read or write it.
+struct DevScratch {
+    int dev;
+    size_t bytes;
+    hipStream_t s;
+    std::vector<uint8_t *> bufs = {};
+    ~DevScratch() {
+        if (!bufs.empty()) (void)hipStreamSynchronize(s);
+        for (uint8_t *p : bufs) dev_cache().release(dev, p, bytes);
+    }
+    int take(const char *op, uint8_t **p) {
+        if (!(*p = static_cast<uint8_t *>(dev_cache().acquire(dev, bytes))))
+            return fail(CEC_ENOMEM, "%s: device scratch", op);
+        bufs.push_back(*p);
+        return CEC_OK;
+    }
+};
+
+// The device view of the residual parity `lid` shipped (the whole range): in place, or, if
+// pageable, staged into scratch of `tmp` (enqueued on s).
+static int peer_residual(cec_recovery *r, const char *op, const void *const *peer_residuals, int lid,
+                         DevScratch &tmp, hipStream_t s, const uint8_t **dv) {
+    if (!peer_residuals || !peer_residuals[lid]) return fail(CEC_EINVAL, "%s: residual of parity %d missing", op, lid);
+    uint8_t *stage = nullptr;
+    if (!device_view_of(peer_residuals[lid]))
+        if (int rc = tmp.take(op, &stage)) return rc;
+    return device_input(r, peer_residuals[lid], r->nbuf, stage, s, dv);
+}
+
 CEC_API int cec_recovery_add_peer(cec_recovery *r, int peer, const void *units, void *stream) {
-    if (!r || !units || peer < 0 || peer >= r->k || !(r->mask & (1u << peer)))
+    if (!r || !units || peer < 0 || peer >= r->code.k || !(r->mask & (1u << peer)))
         return fail(CEC_EINVAL, "cec_recovery_add_peer: peer %d is not a data lid of the mask", peer);
     if (r->contributed & (1u << peer))
         return fail(CEC_EINVAL, "cec_recovery_add_peer: peer %d already applied (recovery.c:75)", peer);
@@ -235,25 +265,12 @@ CEC_API int cec_recovery_add_peer(cec_recovery *r, int peer, const void *units, 
     UseNote note_{r->uses, s};
     const uint8_t *d;
     if (int rc = device_input(r, units, r->nbuf, r->scratch, s, &d)) return rc;
-    const int *matrix = r->matrix.data();
-    const int k = r->k;
     Streams st;
-    st.base[0] = const_cast<uint8_t *>(d);
-    st.base[1] = r->residual;
-    st.base[2] = const_cast<uint8_t *>(r->parity);
+    const int s_units = st.add(d), s_residual = st.add(r->residual), s_parity = st.add(r->parity);
     Combo c;
-    Combo::Out o{};
-    o.stream = 1;
-    c.in_stream[c.n_in] = 0;
-    o.coef[c.n_in++] = MATRIX(r->lid_self, peer);  // recovery.c:91-93
-    if (!r->touched) {  // first touch: R = P ^ c*D (recovery.c:79-82 + 91)
-        c.in_stream[c.n_in] = 2;
-        o.coef[c.n_in++] = 1;
-        o.mode = kModeWrite;
-    } else {
-        o.mode = kModeXor;
-    }
-    c.outs.push_back(o);
+    Combo::Out &o = c.out(s_residual, r->touched ? kModeXor : kModeWrite);
+    o.coef[c.in(s_units)] = r->code.at(r->lid_self, peer);  // recovery.c:91-93
+    if (!r->touched) o.coef[c.in(s_parity)] = 1;            // first touch: R = P ^ c*D (recovery.c:79-82 + 91)
     if (int rc = run_combos_region(dev, st, {c}, r->nbuf, s)) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     r->touched = true;
@@ -263,7 +280,7 @@ CEC_API int cec_recovery_add_peer(cec_recovery *r, int peer, const void *units, 
 
 CEC_API int cec_recovery_fold_update(cec_recovery *r, int peer, uint64_t addr, const void *diff,
                                      uint32_t len, void *stream) {
-    if (!r || (len && !diff) || peer < 0 || peer >= r->k)
+    if (!r || (len && !diff) || peer < 0 || peer >= r->code.k)
         return fail(CEC_EINVAL, "cec_recovery_fold_update: bad args");
     // recovery.c:116-119: units not touched yet pick the update up from the parity
     // arena at first touch; a peer that already contributed sent post-update bytes.
@@ -277,9 +294,7 @@ CEC_API int cec_recovery_fold_update(cec_recovery *r, int peer, uint64_t addr, c
     const uint8_t *piece = static_cast<const uint8_t *>(diff) + (lo - addr);
     const uint8_t *d;
     if (int rc = device_input(r, piece, hi - lo, r->scratch, s, &d)) return rc;
-    const int *matrix = r->matrix.data();
-    const int k = r->k;
-    if (int rc = cec_region_multiply(d, MATRIX(r->lid_self, peer), hi - lo, r->residual + (lo - r->base),
+    if (int rc = cec_region_multiply(d, r->code.at(r->lid_self, peer), hi - lo, r->residual + (lo - r->base),
                                      1, s))
         return rc;
     if (int rc = stream_wait(s, false)) return rc;  // per-SET call: its latency is its cost (residual in HBM)
@@ -288,7 +303,7 @@ CEC_API int cec_recovery_fold_update(cec_recovery *r, int peer, uint64_t addr, c
 
 CEC_API int cec_recovery_complete(const cec_recovery *r) {
     if (!r) return 0;
-    const uint32_t data = r->mask & ((1u << r->k) - 1);
+    const uint32_t data = r->mask & ((1u << r->code.k) - 1);
     return (r->contributed & data) == data ? 1 : 0;
 }
 
@@ -304,71 +319,37 @@ CEC_API int cec_recovery_solve(cec_recovery *r, const void *const *peer_residual
     if (int rc = current_device(&dev)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     UseNote note_{r->uses, s};
-    const int k = r->k, m = r->m;
-    const int *matrix = r->matrix.data();
-    int lost[CEC_MAX_K], pars[CEC_MAX_M], inv[CEC_MAX_M * CEC_MAX_M];
-    const int n = mask_split(k, m, r->mask, lost, pars);
-    if (n <= 0) return n == 0 ? CEC_OK : fail(CEC_EINVAL, "cec_recovery_solve: bad mask");
-    if (solve_inverse(k, matrix, n, lost, pars, inv))
-        return fail(CEC_ESINGULAR, "cec_recovery_solve: singular submatrix for mask 0x%x", r->mask);
-    std::vector<uint8_t *> temp;  // device scratch for staged inputs / host outputs
-    auto cleanup = [&] {
-        if (!temp.empty()) (void)hipStreamSynchronize(s);
-        for (uint8_t *p : temp) dev_cache().release(r->device, p, r->nbuf);
-    };
-    auto scratch = [&](uint8_t **p) -> int {
-        if (!(*p = static_cast<uint8_t *>(dev_cache().acquire(r->device, r->nbuf))))
-            return fail(CEC_ENOMEM, "cec_recovery_solve: device scratch");
-        temp.push_back(*p);
-        return CEC_OK;
-    };
+    Loss ls;
+    if (int rc = Loss::of(r->code, r->mask, "cec_recovery_solve", &ls)) return rc;
+    if (ls.n == 0) return CEC_OK;
+    DevScratch tmp{r->device, r->nbuf, s};  // staged inputs / host outputs
     Streams st;
     Combo c;
-    c.n_in = n;
-    for (int j = 0; j < n; ++j) {
-        const uint8_t *cj;
-        if (pars[j] == r->lid_self) {
-            cj = r->residual;
-        } else {
-            if (!peer_residuals || !peer_residuals[pars[j]]) {
-                cleanup();
-                return fail(CEC_EINVAL, "cec_recovery_solve: residual of parity %d missing", pars[j]);
-            }
-            uint8_t *tmp = nullptr;
-            const void *pr = peer_residuals[pars[j]];
-            if (!device_view_of(pr)) {
-                if (int rc = scratch(&tmp)) { cleanup(); return rc; }
-            }
-            if (int rc = device_input(r, pr, r->nbuf, tmp, s, &cj)) { cleanup(); return rc; }
-        }
-        st.base[j] = const_cast<uint8_t *>(cj);
-        c.in_stream[j] = static_cast<uint8_t>(j);
+    for (int j = 0; j < ls.n; ++j) {
+        const uint8_t *cj = r->residual;
+        if (ls.pars[j] != r->lid_self)
+            if (int rc = peer_residual(r, "cec_recovery_solve", peer_residuals, ls.pars[j], tmp, s, &cj)) return rc;
+        c.in(st.add(cj));
     }
     std::vector<std::pair<uint8_t *, uint8_t *>> downloads;  // (host dst, device src)
-    for (int x = 0; x < n; ++x) {
-        void *o = out[lost[x]];
-        if (!o) { cleanup(); return fail(CEC_EINVAL, "cec_recovery_solve: out[%d] is NULL", lost[x]); }
+    for (int x = 0; x < ls.n; ++x) {
+        void *o = out[ls.lost[x]];
+        if (!o) return fail(CEC_EINVAL, "cec_recovery_solve: out[%d] is NULL", ls.lost[x]);
         uint8_t *dv = static_cast<uint8_t *>(device_view_of(o));
         if (!dv) {
-            if (int rc = scratch(&dv)) { cleanup(); return rc; }
+            if (int rc = tmp.take("cec_recovery_solve", &dv)) return rc;
             downloads.emplace_back(static_cast<uint8_t *>(o), dv);
         }
-        st.base[CEC_MAX_M + x] = dv;
-        Combo::Out q{};
-        q.stream = static_cast<uint8_t>(CEC_MAX_M + x);
-        q.mode = kModeWrite;  // data[i] = calloc, then += (memcached.c:7913-7922)
-        for (int j = 0; j < n; ++j) q.coef[j] = inv[x * n + j];
-        c.outs.push_back(q);
+        Combo::Out &q = c.out(st.add(dv), kModeWrite);  // data[i] = calloc, then += (memcached.c:7913-7922)
+        for (int j = 0; j < ls.n; ++j) q.coef[j] = ls.at(x, j);
     }
-    if (int rc = run_combos_region(dev, st, {c}, r->nbuf, s)) { cleanup(); return rc; }
+    if (int rc = run_combos_region(dev, st, {c}, r->nbuf, s)) return rc;
     for (auto &dl : downloads)
-        if (int rc = r->stager.download(dl.first, dl.second, r->nbuf, s)) { cleanup(); return rc; }
+        if (int rc = r->stager.download(dl.first, dl.second, r->nbuf, s)) return rc;
     // Synchronous (cocytus_ec.h): out, device or pinned, holds the rebuilt bytes on return,
     // and the caller may reuse its peer-residual buffers.
     // (the system-scope fence only when the kernel wrote host-visible memory directly)
-    const int rc = stream_wait(s, any_host_memory(reinterpret_cast<uint8_t *const *>(out), k));
-    cleanup();
-    return rc;
+    return stream_wait(s, any_host_memory(reinterpret_cast<uint8_t *const *>(out), r->code.k));
 }
 
 // The last data peer's fold (recovery_recover_units, recovery.c:61-96) and the leader
@@ -383,11 +364,11 @@ CEC_API int cec_recovery_solve(cec_recovery *r, const void *const *peer_residual
 // (21.9 vs 17.5 ms for 256 MiB) because it serialises the pack and unpack copies.
 CEC_API int cec_recovery_finish(cec_recovery *r, int peer, const void *units,
                                 const void *const *peer_residuals, void *const *out, void *stream) {
-    if (!r || !units || !out || peer < 0 || peer >= r->k || !(r->mask & (1u << peer)))
+    if (!r || !units || !out || peer < 0 || peer >= r->code.k || !(r->mask & (1u << peer)))
         return fail(CEC_EINVAL, "cec_recovery_finish: peer %d is not a data lid of the mask", peer);
     if (r->contributed & (1u << peer))
         return fail(CEC_EINVAL, "cec_recovery_finish: peer %d already applied (recovery.c:75)", peer);
-    const uint32_t data_lids = r->mask & ((1u << r->k) - 1);
+    const uint32_t data_lids = r->mask & ((1u << r->code.k) - 1);
     if (((r->contributed | (1u << peer)) & data_lids) != data_lids)
         return fail(CEC_EINVAL, "cec_recovery_finish: peer %d is not the last data peer of mask 0x%x",
                     peer, r->mask);
@@ -395,100 +376,47 @@ CEC_API int cec_recovery_finish(cec_recovery *r, int peer, const void *units,
     if (int rc = current_device(&dev)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     UseNote note_{r->uses, s};
-    const int k = r->k, m = r->m;
-    const int *matrix = r->matrix.data();
-    int lost[CEC_MAX_K], pars[CEC_MAX_M], inv[CEC_MAX_M * CEC_MAX_M];
-    const int n = mask_split(k, m, r->mask, lost, pars);
-    if (n < 0) return fail(CEC_EINVAL, "cec_recovery_finish: bad mask");
-    if (n == 0) {  // nothing lost: the fold alone
-        if (int rc = cec_recovery_add_peer(r, peer, units, stream)) return rc;
-        return CEC_OK;
-    }
-    if (solve_inverse(k, matrix, n, lost, pars, inv))
-        return fail(CEC_ESINGULAR, "cec_recovery_finish: singular submatrix for mask 0x%x", r->mask);
-    int self = -1;
-    for (int j = 0; j < n; ++j)
-        if (pars[j] == r->lid_self) self = j;
+    Loss ls;
+    if (int rc = Loss::of(r->code, r->mask, "cec_recovery_finish", &ls)) return rc;
+    if (ls.n == 0) return cec_recovery_add_peer(r, peer, units, stream);  // nothing lost: the fold alone
+    const int self = ls.index_of_parity(r->lid_self);
     bool pageable = device_view_of(units) == nullptr;
-    for (int x = 0; x < n; ++x) {
-        if (!out[lost[x]]) return fail(CEC_EINVAL, "cec_recovery_finish: out[%d] is NULL", lost[x]);
-        pageable |= device_view_of(out[lost[x]]) == nullptr;
+    for (int x = 0; x < ls.n; ++x) {
+        if (!out[ls.lost[x]]) return fail(CEC_EINVAL, "cec_recovery_finish: out[%d] is NULL", ls.lost[x]);
+        pageable |= device_view_of(out[ls.lost[x]]) == nullptr;
     }
     if (self < 0 || pageable) {  // not a leader solve, or host bytes to stage
         if (int rc = cec_recovery_add_peer(r, peer, units, stream)) return rc;
         return cec_recovery_solve(r, peer_residuals, out, stream);
     }
-    std::vector<uint8_t *> temp;
-    auto cleanup = [&] {
-        if (!temp.empty()) (void)hipStreamSynchronize(s);
-        for (uint8_t *q : temp) dev_cache().release(r->device, q, r->nbuf);
-    };
-    auto scratch = [&](uint8_t **q) -> int {
-        if (!(*q = static_cast<uint8_t *>(dev_cache().acquire(r->device, r->nbuf))))
-            return fail(CEC_ENOMEM, "cec_recovery_finish: device scratch");
-        temp.push_back(*q);
-        return CEC_OK;
-    };
-    // the other participating parities' residuals, staged whole (multi-loss only)
-    const uint8_t *C[CEC_MAX_M] = {};
-    for (int j = 0; j < n; ++j) {
-        if (j == self) continue;
-        if (!peer_residuals || !peer_residuals[pars[j]]) {
-            cleanup();
-            return fail(CEC_EINVAL, "cec_recovery_finish: residual of parity %d missing", pars[j]);
-        }
-        uint8_t *tmp = nullptr;
-        if (!device_view_of(peer_residuals[pars[j]])) {
-            if (int rc = scratch(&tmp)) { cleanup(); return rc; }
-        }
-        if (int rc = device_input(r, peer_residuals[pars[j]], r->nbuf, tmp, s, &C[j])) { cleanup(); return rc; }
-    }
-    const uint8_t *din = static_cast<const uint8_t *>(device_view_of(units));
-    uint8_t *dout[CEC_MAX_M] = {};
-    for (int x = 0; x < n; ++x) dout[x] = static_cast<uint8_t *>(device_view_of(out[lost[x]]));
-    // one combination: inputs D, R_or_P, C_j (j != self); outputs R', out_x
-    const int c = MATRIX(r->lid_self, peer);
-    Combo cb;
-    cb.n_in = 2;
-    cb.in_stream[0] = 0;
-    cb.in_stream[1] = 1;
-    int cin[CEC_MAX_M] = {};
-    for (int j = 0; j < n; ++j)
-        if (j != self) {
-            cin[j] = cb.n_in;
-            cb.in_stream[cb.n_in++] = static_cast<uint8_t>(2 + j);
-        }
-    Combo::Out ro{};
-    ro.stream = 2 + CEC_MAX_M;
-    ro.mode = kModeWrite;
-    ro.coef[0] = c;
-    ro.coef[1] = 1;
-    cb.outs.push_back(ro);
-    for (int x = 0; x < n; ++x) {
-        Combo::Out q{};
-        q.stream = static_cast<uint8_t>(3 + CEC_MAX_M + x);
-        q.mode = kModeWrite;  // data[i] = calloc, then += (memcached.c:7913-7922)
-        const int is = inv[x * n + self];
-        q.coef[0] = gf_mul(is, c);
-        q.coef[1] = is;
-        for (int j = 0; j < n; ++j)
-            if (j != self) q.coef[cin[j]] = inv[x * n + j];
-        cb.outs.push_back(q);
-    }
-    const uint8_t *rp = r->touched ? r->residual : r->parity;
+    DevScratch tmp{r->device, r->nbuf, s};
+    // one combination: inputs D, R_or_P, C_j (j != self), the other participating parities'
+    // residuals, staged whole (multi-loss only); outputs R', out_x
+    const int c = r->code.at(r->lid_self, peer);
     Streams st;
-    st.base[0] = const_cast<uint8_t *>(din);
-    st.base[1] = const_cast<uint8_t *>(rp);
-    for (int j = 0; j < n; ++j)
-        if (j != self) st.base[2 + j] = const_cast<uint8_t *>(C[j]);
-    st.base[2 + CEC_MAX_M] = r->residual;
-    for (int x = 0; x < n; ++x) st.base[3 + CEC_MAX_M + x] = dout[x];
-    if (int rc = run_combos_region(dev, st, {cb}, r->nbuf, s)) { cleanup(); return rc; }
+    Combo cb;
+    const int in_d = cb.in(st.add(device_view_of(units)));
+    int in_res[CEC_MAX_M];  // the input that carries the residual of parity pars[j]
+    in_res[self] = cb.in(st.add(r->touched ? r->residual : r->parity));
+    for (int j = 0; j < ls.n; ++j) {
+        if (j == self) continue;
+        const uint8_t *cj;
+        if (int rc = peer_residual(r, "cec_recovery_finish", peer_residuals, ls.pars[j], tmp, s, &cj)) return rc;
+        in_res[j] = cb.in(st.add(cj));
+    }
+    Combo::Out &ro = cb.out(st.add(r->residual), kModeWrite);
+    ro.coef[in_d] = c;
+    ro.coef[in_res[self]] = 1;
+    for (int x = 0; x < ls.n; ++x) {
+        // data[i] = calloc, then += (memcached.c:7913-7922)
+        Combo::Out &q = cb.out(st.add(device_view_of(out[ls.lost[x]])), kModeWrite);
+        q.coef[in_d] = gf_mul(ls.at(x, self), c);
+        for (int j = 0; j < ls.n; ++j) q.coef[in_res[j]] = ls.at(x, j);
+    }
+    if (int rc = run_combos_region(dev, st, {cb}, r->nbuf, s)) return rc;
     // Synchronous (cocytus_ec.h): the rebuilt bytes are in out on return, and units /
     // peer residuals may be reused by the caller.
-    const int rc = stream_wait(s, any_host_memory(reinterpret_cast<uint8_t *const *>(out), k));
-    cleanup();
-    if (rc) return rc;
+    if (int rc = stream_wait(s, any_host_memory(reinterpret_cast<uint8_t *const *>(out), r->code.k))) return rc;
     r->touched = true;
     r->contributed |= 1u << peer;
     return CEC_OK;

@@ -280,9 +280,7 @@ static bool exact_shape(const std::vector<Pattern> &pats, const std::vector<char
     return true;
 }
 
-struct Streams {
-    uint8_t *base[kMaxStreams] = {};
-};
+#include "cec_combo.inc"
 
 // ============================================================== plans
 // Tiles of one extent end on 4 KiB boundaries of the arena offset, so interior
@@ -672,6 +670,7 @@ static bool layout_ok_for(const CombineArgs &a, const CombineArgsN<kNarrowStream
 // (kFlagSysRelease asked for, and honoured: only the narrow 1 x 1 launches carry it).
 static int launch_combine(int dev, const Streams &st, const Tables &tb, const LaunchShape &sh, bool lds,
                           const TileSource &src, hipStream_t stream, uint32_t flags = 0, bool *released = nullptr) {
+    if (st.refused) return fail(CEC_EINVAL, "internal: an op names more than %d byte streams; not launched", kMaxStreams);
     CombineArgs a;
     memset(&a, 0, sizeof a);
     a.flags = flags;
@@ -753,18 +752,6 @@ static int run_combine(int dev, const Streams &st, const std::vector<Pattern> &p
     HIP_TRY(hipGetLastError());
     return CEC_OK;
 }
-
-// Logical pattern with arbitrarily many outputs, before splitting.
-struct Combo {
-    int n_in = 0;
-    uint8_t in_stream[kPatN] = {};
-    uint8_t in_src[kPatN] = {};
-    struct Out {
-        uint8_t stream, src, mode;
-        int coef[kPatN];
-    };
-    std::vector<Out> outs;  // install output (if any) is last
-};
 
 // The patterns of launch g of a combo list: outputs [4g, 4g+4) of every combo (an
 // install output is last in `outs`, so it runs in the final launch after every group
@@ -849,8 +836,6 @@ static int check_code(int k, int m, const int *matrix) {
             return fail(CEC_EINVAL, "matrix entry %d = %d outside GF(2^8)", i, matrix[i]);
     return CEC_OK;
 }
-
-#define MATRIX(x, y) matrix[(x) * k + (y)]
 
 // ============================================================== arena layout
 CEC_API size_t cec_arena_stride(size_t bytes) {
@@ -961,22 +946,13 @@ static int region_launch(int dev, const void *src, int multby, size_t n, void *d
     const int key = (engine << 9) | (add ? 256 : 0) | multby;
     const bool capturing = !plain && stream_capturing(s);
     Streams st;
-    st.base[0] = static_cast<uint8_t *>(const_cast<void *>(src));
-    st.base[1] = static_cast<uint8_t *>(dst);
+    const int s_src = st.add(src), s_dst = st.add(dst);
     RegionMemo once;            // while capturing: tables pinned for this launch only
     RegionMemo *m = &t_region;  // the tables this launch runs with
     if (!(m->e && m->dev == dev && m->key == key && !capturing && m->e->up_done.load(std::memory_order_acquire))) {
-        Combo cb;
-        cb.n_in = 1;
-        cb.in_stream[0] = 0;
-        Combo::Out o{};
-        o.stream = 1;
-        o.mode = add ? kModeXor : kModeWrite;
-        o.coef[0] = multby;
-        cb.outs.push_back(o);
         std::vector<Pattern> pats;
         std::vector<uint8_t> rows;
-        if (int r = build_patterns({cb}, 0, engine, pats, rows, true)) return r;
+        if (int r = build_patterns({multiply_combo(multby, add, s_src, s_dst)}, 0, engine, pats, rows, true)) return r;
         PatEntry *e = nullptr;
         if (int r = pattern_tables(dev, pats, rows, s, &e)) return r;
         if (capturing) m = &once;           // (the cache marked the tables captured)
@@ -1025,22 +1001,18 @@ static int encode_common(int k, int m, const int *matrix, const uint8_t *const *
     if (!data || !parity) return fail(CEC_EINVAL, "cec_encode: NULL arena array");
     int dev;
     if (int r = current_device(&dev)) return r;
+    const Code code{k, m, matrix};
     Streams st;
     Combo c;
-    c.n_in = k;
     for (int j = 0; j < k; ++j) {
         if (!data[j]) return fail(CEC_EINVAL, "cec_encode: data[%d] is NULL", j);
-        st.base[j] = const_cast<uint8_t *>(data[j]);
-        c.in_stream[j] = static_cast<uint8_t>(j);
+        c.in(st.add(data[j]));
     }
     for (int p = 0; p < m; ++p) {
+        const int slot = st.add(parity[p]);
         if (!parity[p]) continue;  // a lost parity is simply not produced
-        st.base[k + p] = parity[p];
-        Combo::Out o{};
-        o.stream = static_cast<uint8_t>(k + p);
-        o.mode = kModeWrite;
-        for (int j = 0; j < k; ++j) o.coef[j] = MATRIX(k + p, j);
-        c.outs.push_back(o);
+        Combo::Out &o = c.out(slot, kModeWrite);
+        for (int j = 0; j < k; ++j) o.coef[j] = code.at(k + p, j);
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     return plan ? run_combos_plan(dev, st, {c}, plan, s) : run_combos_region(dev, st, {c}, len, s);
@@ -1075,36 +1047,26 @@ CEC_API int cec_diff_update(int k, int m, const int *matrix, uint8_t *const *dat
         return fail(CEC_EINVAL, "cec_diff_update: an extent names source shard %u (k = %d)", plan->max_pattern, k);
     int dev;
     if (int r = current_device(&dev)) return r;
+    const Code code{k, m, matrix};
     Streams st;
+    int s_data[CEC_MAX_K], s_parity[CEC_MAX_M];
     for (int j = 0; j < k; ++j) {
         if (!data[j]) return fail(CEC_EINVAL, "cec_diff_update: data[%d] is NULL", j);
-        st.base[j] = data[j];
+        s_data[j] = st.add(data[j]);
     }
-    for (int p = 0; p < m; ++p) st.base[k + p] = parity[p];
-    st.base[k + m] = const_cast<uint8_t *>(staging);
+    for (int p = 0; p < m; ++p) s_parity[p] = st.add(parity[p]);
+    const int s_staging = st.add(staging);
     std::vector<Combo> combos(k);
     for (int j = 0; j < k; ++j) {
         Combo &c = combos[j];
-        c.n_in = 2;
-        c.in_stream[0] = static_cast<uint8_t>(j);      // old bytes, arena offset
-        c.in_stream[1] = static_cast<uint8_t>(k + m);  // new value, staging offset
-        c.in_src[1] = 1;
+        const int old = c.in(s_data[j]);          // old bytes, arena offset
+        const int nu = c.in(s_staging, true);     // new value, staging offset
         for (int p = 0; p < m; ++p) {
             if (!parity[p]) continue;  // lost parity: skipped like memcached.c:2692-2694
-            Combo::Out o{};
-            o.stream = static_cast<uint8_t>(k + p);
-            o.mode = kModeXor;
-            o.coef[0] = o.coef[1] = MATRIX(k + p, j);
-            c.outs.push_back(o);
+            Combo::Out &o = c.out(s_parity[p], kModeXor);
+            o.coef[old] = o.coef[nu] = code.at(k + p, j);
         }
-        if (install) {
-            Combo::Out o{};
-            o.stream = static_cast<uint8_t>(j);
-            o.mode = kModeWrite;
-            o.coef[0] = 0;
-            o.coef[1] = 1;
-            c.outs.push_back(o);
-        }
+        if (install) c.out(s_data[j], kModeWrite).coef[nu] = 1;
     }
     // AUTO: PERM.  The LDS engine's diff-update was within +-3 % of PERM either way over
     // the recorded boxes (median margin under 1 %; DESIGN.md §4 "Engine per op").
@@ -1120,25 +1082,18 @@ CEC_API int cec_set_diff(int k, const uint8_t *const *data, const uint8_t *stagi
     int dev;
     if (int r = current_device(&dev)) return r;
     Streams st;
+    int s_data[CEC_MAX_K];
     for (int j = 0; j < k; ++j) {
         if (!data[j]) return fail(CEC_EINVAL, "cec_set_diff: data[%d] is NULL", j);
-        st.base[j] = const_cast<uint8_t *>(data[j]);
+        s_data[j] = st.add(data[j]);
     }
-    st.base[k] = const_cast<uint8_t *>(staging);
-    st.base[k + 1] = diff;
+    const int s_staging = st.add(staging), s_diff = st.add(diff);
     std::vector<Combo> combos(k);
     for (int j = 0; j < k; ++j) {
         Combo &c = combos[j];
-        c.n_in = 2;
-        c.in_stream[0] = static_cast<uint8_t>(j);
-        c.in_stream[1] = static_cast<uint8_t>(k);
-        c.in_src[1] = 1;
-        Combo::Out o{};
-        o.stream = static_cast<uint8_t>(k + 1);
-        o.src = 1;
-        o.mode = kModeWrite;
-        o.coef[0] = o.coef[1] = 1;
-        c.outs.push_back(o);
+        const int old = c.in(s_data[j]), nu = c.in(s_staging, true);
+        Combo::Out &o = c.out(s_diff, kModeWrite, true);
+        o.coef[old] = o.coef[nu] = 1;
     }
     return run_combos_plan(dev, st, combos, plan, static_cast<hipStream_t>(stream));
 }
@@ -1153,27 +1108,8 @@ CEC_API int cec_apply_diffs(int k, int m, const int *matrix, int lid_self, const
         return fail(CEC_EINVAL, "cec_apply_diffs: an extent names source shard %u (k = %d)", plan->max_pattern, k);
     int dev;
     if (int r = current_device(&dev)) return r;
-    Streams st;
-    st.base[0] = const_cast<uint8_t *>(diffs);
-    st.base[1] = parity;
-    std::vector<Combo> combos(k);
-    for (int j = 0; j < k; ++j) {
-        Combo &c = combos[j];
-        c.n_in = 1;
-        c.in_stream[0] = 0;
-        c.in_src[0] = 1;
-        Combo::Out o{};
-        o.stream = 1;
-        o.mode = kModeXor;
-        o.coef[0] = MATRIX(lid_self, j);
-        c.outs.push_back(o);
-    }
-    return run_combos_plan(dev, st, combos, plan, static_cast<hipStream_t>(stream));
-}
-
-static int mask_ok(int k, int m, uint32_t mask) {
-    if (k + m < 32 && (mask >> (k + m)) != 0) return 0;
-    return __builtin_popcount(mask) == k;
+    const Fold f = fold(Code{k, m, matrix}, lid_self, diffs, parity);
+    return run_combos_plan(dev, f.st, f.combos, plan, static_cast<hipStream_t>(stream));
 }
 
 CEC_API int cec_residual(int k, int m, const int *matrix, int lid_self, uint32_t mask,
@@ -1190,44 +1126,21 @@ CEC_API int cec_residual(int k, int m, const int *matrix, int lid_self, uint32_t
                                 "than the %d inputs of one combination", mask, n_data, kPatN);
     int dev;
     if (int r = current_device(&dev)) return r;
-    Streams st;
-    Combo c;
-    Combo::Out o{};
-    o.stream = static_cast<uint8_t>(k + m);
-    o.mode = kModeWrite;
     if (!arenas[lid_self]) return fail(CEC_EINVAL, "cec_residual: own parity arena is NULL");
-    st.base[lid_self] = const_cast<uint8_t *>(arenas[lid_self]);
-    c.in_stream[c.n_in] = static_cast<uint8_t>(lid_self);
-    o.coef[c.n_in++] = 1;  // first touch copies the parity unit (recovery.c:79-82)
-    for (int s = 0; s < k; ++s) {
-        if (!(mask & (1u << s))) continue;
-        if (!arenas[s]) return fail(CEC_EINVAL, "cec_residual: arena %d in mask is NULL", s);
-        st.base[s] = const_cast<uint8_t *>(arenas[s]);
-        c.in_stream[c.n_in] = static_cast<uint8_t>(s);
-        o.coef[c.n_in++] = MATRIX(lid_self, s);  // recovery.c:91-93
-    }
-    st.base[k + m] = residual;
-    c.outs.push_back(o);
+    for (int s = 0; s < k; ++s)
+        if ((mask & (1u << s)) && !arenas[s]) return fail(CEC_EINVAL, "cec_residual: arena %d in mask is NULL", s);
+    const Code code{k, m, matrix};
+    // one slot per lid, empty unless the combination reads it, then the residual's
+    Streams st;
+    int s_lid[CEC_MAX_K + CEC_MAX_M];
+    for (int lid = 0; lid < k + m; ++lid)
+        s_lid[lid] = st.add(lid == lid_self || (lid < k && (mask & (1u << lid))) ? arenas[lid] : nullptr);
+    Combo c;
+    Combo::Out &o = c.out(st.add(residual), kModeWrite);
+    o.coef[c.in(s_lid[lid_self])] = 1;  // first touch copies the parity unit (recovery.c:79-82)
+    for (int s = 0; s < k; ++s)
+        if (mask & (1u << s)) o.coef[c.in(s_lid[s])] = code.at(lid_self, s);  // recovery.c:91-93
     return run_combos_plan(dev, st, {c}, plan, static_cast<hipStream_t>(stream));
-}
-
-// Lost data lids and participating parity lids of a recovery mask, ascending
-// (complete_recovery_bottom_half, memcached.c:7847-7894).
-static int mask_split(int k, int m, uint32_t mask, int *lost, int *pars) {
-    int n = 0, r = 0;
-    for (int j = 0; j < k; ++j)
-        if (!(mask & (1u << j))) lost[n++] = j;
-    for (int p = k; p < k + m; ++p)
-        if (mask & (1u << p)) pars[r++] = p;
-    return n == r ? n : -1;
-}
-
-static int solve_inverse(int k, const int *matrix, int n, const int *lost, const int *pars,
-                         int *inv) {
-    int tmp[CEC_MAX_M * CEC_MAX_M];
-    for (int r = 0; r < n; ++r)
-        for (int c = 0; c < n; ++c) tmp[r * n + c] = MATRIX(pars[r], lost[c]);
-    return invert_matrix(tmp, inv, n);
 }
 
 CEC_API int cec_solve(int k, int m, const int *matrix, uint32_t mask,
@@ -1239,28 +1152,19 @@ CEC_API int cec_solve(int k, int m, const int *matrix, uint32_t mask,
     if (int r = single_pattern_plan(plan, "cec_solve")) return r;
     int dev;
     if (int r = current_device(&dev)) return r;
-    int lost[CEC_MAX_K], pars[CEC_MAX_M], inv[CEC_MAX_M * CEC_MAX_M];
-    const int n = mask_split(k, m, mask, lost, pars);
-    if (n < 0) return fail(CEC_EINVAL, "cec_solve: mask 0x%x is not a recovery mask", mask);
-    if (n == 0) return CEC_OK;
-    if (solve_inverse(k, matrix, n, lost, pars, inv))
-        return fail(CEC_ESINGULAR, "cec_solve: singular submatrix for mask 0x%x", mask);
+    Loss ls;
+    if (int r = Loss::of(Code{k, m, matrix}, mask, "cec_solve", &ls)) return r;
+    if (ls.n == 0) return CEC_OK;
     Streams st;
     Combo c;
-    c.n_in = n;
-    for (int r = 0; r < n; ++r) {
-        if (!residuals[pars[r]]) return fail(CEC_EINVAL, "cec_solve: residual %d NULL", pars[r]);
-        st.base[r] = const_cast<uint8_t *>(residuals[pars[r]]);
-        c.in_stream[r] = static_cast<uint8_t>(r);
+    for (int r = 0; r < ls.n; ++r) {
+        if (!residuals[ls.pars[r]]) return fail(CEC_EINVAL, "cec_solve: residual %d NULL", ls.pars[r]);
+        c.in(st.add(residuals[ls.pars[r]]));
     }
-    for (int x = 0; x < n; ++x) {
-        if (!out[lost[x]]) return fail(CEC_EINVAL, "cec_solve: out[%d] NULL", lost[x]);
-        st.base[CEC_MAX_M + x] = out[lost[x]];
-        Combo::Out o{};
-        o.stream = static_cast<uint8_t>(CEC_MAX_M + x);
-        o.mode = kModeWrite;
-        for (int r = 0; r < n; ++r) o.coef[r] = inv[x * n + r];  // memcached.c:7916-7922
-        c.outs.push_back(o);
+    for (int x = 0; x < ls.n; ++x) {
+        if (!out[ls.lost[x]]) return fail(CEC_EINVAL, "cec_solve: out[%d] NULL", ls.lost[x]);
+        Combo::Out &o = c.out(st.add(out[ls.lost[x]]), kModeWrite);
+        for (int r = 0; r < ls.n; ++r) o.coef[r] = ls.at(x, r);  // memcached.c:7916-7922
     }
     return run_combos_plan(dev, st, {c}, plan, static_cast<hipStream_t>(stream));
 }
@@ -1275,42 +1179,30 @@ CEC_API int cec_decode(int k, int m, const int *matrix, const uint32_t *masks, i
     if (int r = current_device(&dev)) return r;
     if (plan->n_ext && plan->max_pattern >= static_cast<uint32_t>(n_masks))
         return fail(CEC_EINVAL, "cec_decode: an extent names mask %u of %d", plan->max_pattern, n_masks);
+    const Code code{k, m, matrix};
     Streams st;
-    for (int lid = 0; lid < k + m; ++lid) st.base[lid] = const_cast<uint8_t *>(arenas[lid]);
-    for (int j = 0; j < k; ++j) st.base[k + m + j] = out[j];
+    int s_arena[CEC_MAX_K + CEC_MAX_M], s_out[CEC_MAX_K];
+    for (int lid = 0; lid < k + m; ++lid) s_arena[lid] = st.add(arenas[lid]);
+    for (int j = 0; j < k; ++j) s_out[j] = st.add(out[j]);
     std::vector<Combo> combos(n_masks);
     for (int q = 0; q < n_masks; ++q) {
         const uint32_t mask = masks[q];
-        if (!mask_ok(k, m, mask)) return fail(CEC_EINVAL, "cec_decode: bad mask 0x%x", mask);
-        int lost[CEC_MAX_K], pars[CEC_MAX_M], inv[CEC_MAX_M * CEC_MAX_M];
-        const int n = mask_split(k, m, mask, lost, pars);
-        if (n < 0) return fail(CEC_EINVAL, "cec_decode: mask 0x%x is not a recovery mask", mask);
-        if (n > 0 && solve_inverse(k, matrix, n, lost, pars, inv))
-            return fail(CEC_ESINGULAR, "cec_decode: singular submatrix for mask 0x%x", mask);
+        Loss ls;
+        if (int r = Loss::of(code, mask, "cec_decode", &ls)) return r;
         Combo &c = combos[q];
         // inputs: the n participating parities, then the k-n surviving data shards
-        int surv[CEC_MAX_K], ns = 0;
-        for (int j = 0; j < k; ++j)
-            if (mask & (1u << j)) surv[ns++] = j;
-        for (int r = 0; r < n; ++r) c.in_stream[c.n_in++] = static_cast<uint8_t>(pars[r]);
-        for (int s = 0; s < ns; ++s) c.in_stream[c.n_in++] = static_cast<uint8_t>(surv[s]);
-        for (int i = 0; i < c.n_in; ++i)
-            if (!arenas[c.in_stream[i]])
-                return fail(CEC_EINVAL, "cec_decode: arena %d (in mask 0x%x) is NULL",
-                            c.in_stream[i], mask);
-        // D_lost[x] = sum_r inv[x][r] * (P_r ^ sum_s MATRIX(P_r, s) * D_s)
-        for (int x = 0; x < n; ++x) {
-            if (!out[lost[x]]) return fail(CEC_EINVAL, "cec_decode: out[%d] is NULL", lost[x]);
-            Combo::Out o{};
-            o.stream = static_cast<uint8_t>(k + m + lost[x]);
-            o.mode = kModeWrite;
-            for (int r = 0; r < n; ++r) o.coef[r] = inv[x * n + r];
-            for (int s = 0; s < ns; ++s) {
-                int acc = 0;
-                for (int r = 0; r < n; ++r) acc ^= gf_mul(inv[x * n + r], MATRIX(pars[r], surv[s]));
-                o.coef[n + s] = acc;
-            }
-            c.outs.push_back(o);
+        for (int i = 0; i < k; ++i) {
+            const int lid = i < ls.n ? ls.pars[i] : ls.surv[i - ls.n];
+            if (!arenas[lid]) return fail(CEC_EINVAL, "cec_decode: arena %d (in mask 0x%x) is NULL", lid, mask);
+            c.in(s_arena[lid]);
+        }
+        // D_lost[x] = sum_r inv[x][r] * (P_r ^ sum_s M[P_r][s] * D_s)
+        for (int x = 0; x < ls.n; ++x) {
+            if (!out[ls.lost[x]]) return fail(CEC_EINVAL, "cec_decode: out[%d] is NULL", ls.lost[x]);
+            Combo::Out &o = c.out(s_out[ls.lost[x]], kModeWrite);
+            for (int r = 0; r < ls.n; ++r) o.coef[r] = ls.at(x, r);
+            for (int s = 0; s < ls.n_surv; ++s)
+                for (int r = 0; r < ls.n; ++r) o.coef[ls.n + s] ^= gf_mul(ls.at(x, r), code.at(ls.pars[r], ls.surv[s]));
         }
     }
     // AUTO: values of 64 KiB and more (large_values) run the LDS engine, ahead of PERM by a

@@ -111,7 +111,8 @@ CEC_API int cec_scrub_release_stream(cec_scrub_report *s, void *stream) {
 // [0]: the syndrome's coefficients; [1]: ratio[q][j] = MATRIX(k+p0+q, j) / MATRIX(k+p0, j)
 // as PERM tables (a zero denominator leaves the zero table: lid j is then ruled out
 // wherever S_q is non-zero, which errs towards UNLOCATED)
-static std::vector<Pattern> scrub_patterns(int k, const int *matrix, int p0, int lt) {
+static std::vector<Pattern> scrub_patterns(const Code &code, int p0, int lt) {
+    const int k = code.k;
     std::vector<Pattern> pats(2, blank_pattern());
     Pattern &c = pats[0], &r = pats[1];
     c.n_in = r.n_in = k;
@@ -121,9 +122,9 @@ static std::vector<Pattern> scrub_patterns(int k, const int *matrix, int p0, int
         c.out_stream[l] = r.out_stream[l] = k + l;
         c.out_mode[l] = r.out_mode[l] = kModeXor;
         for (int j = 0; j < k; ++j) {
-            set_coef(c, l, j, MATRIX(k + p0 + l, j), CEC_ENGINE_PERM);
-            const int den = MATRIX(k + p0, j);
-            set_coef(r, l, j, l && den ? gf_div(MATRIX(k + p0 + l, j), den) : 0, CEC_ENGINE_PERM);
+            set_coef(c, l, j, code.at(k + p0 + l, j), CEC_ENGINE_PERM);
+            const int den = code.at(k + p0, j);
+            set_coef(r, l, j, l && den ? gf_div(code.at(k + p0 + l, j), den) : 0, CEC_ENGINE_PERM);
         }
     }
     return pats;
@@ -133,12 +134,12 @@ static std::vector<Pattern> scrub_patterns(int k, const int *matrix, int p0, int
 static int scrub_launch(int dev, cec_scrub_report *s, int k, int m, const int *matrix, const uint8_t *const *data,
                         const uint8_t *const *parity, int p0, int lt, const TileSource &src, hipStream_t stream) {
     if (int rc = launch_countdown()) return rc;
-    const std::vector<Pattern> pats = scrub_patterns(k, matrix, p0, lt);
+    const std::vector<Pattern> pats = scrub_patterns(Code{k, m, matrix}, p0, lt);
     ScrubArgs a;
     memset(&a, 0, sizeof a);
     Streams st;  // (for split_shift_for: every base of the launch)
-    for (int j = 0; j < k; ++j) a.base[j] = st.base[j] = const_cast<uint8_t *>(data[j]);
-    for (int l = 0; l < lt; ++l) a.base[k + l] = st.base[k + l] = const_cast<uint8_t *>(parity[p0 + l]);
+    for (int j = 0; j < k; ++j) a.base[st.add(data[j])] = data[j];
+    for (int l = 0; l < lt; ++l) a.base[st.add(parity[p0 + l])] = parity[p0 + l];
     PatEntry *entry = nullptr;
     if (int rc = pattern_tables(dev, pats, {}, stream, &entry)) return rc;
     a.tiles = src.tiles;
@@ -263,7 +264,7 @@ CEC_API int cec_scrub_classify(uint32_t word, int k, int m, const int *matrix) {
     }
     if (lid == CEC_SCRUB_UNLOCATED) return lid;
     uint32_t expect = 0;  // the parities lid j reaches: all m for an MDS matrix
-    for (int p = 0; p < m; ++p) expect |= (MATRIX(k + p, lid) ? 1u : 0u) << p;
+    for (int p = 0; p < m; ++p) expect |= (Code{k, m, matrix}.at(k + p, lid) ? 1u : 0u) << p;
     return syn == expect ? lid : CEC_SCRUB_UNLOCATED;
 }
 

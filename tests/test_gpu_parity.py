@@ -1523,20 +1523,28 @@ def test_recovery_finish_matches_two_step(gpu, oracle, kind):
     assert np.array_equal(outs[1], exp)
 
 
-@pytest.mark.parametrize("outs_kind", ["device", "one_pageable", "two_pageable"])
-def test_recovery_finish_double_loss(gpu, oracle, outs_kind):
+@pytest.mark.parametrize("outs_kind, leader, nunits", [
+    pytest.param("device", 3, 4 * 1024 + 3, id="device"),
+    pytest.param("one_pageable", 3, 4 * 1024 + 3, id="one_pageable"),
+    pytest.param("two_pageable", 3, 4 * 1024 + 3, id="two_pageable"),
+    pytest.param("device", 4, 3, id="leader_second"),
+])
+def test_recovery_finish_double_loss(gpu, oracle, outs_kind, leader, nunits):
     """D0, D1 lost: P1 ships its residual; the leader P0 finishes with the last data peer
-    D2 and rebuilds both shards in the same pass."""
+    D2 and rebuilds both shards in the same pass.  leader_second: P1 finishes and P0 ships,
+    so the leader's own residual is not the first participating parity's (the fused
+    combination's input indices shift by one); D2's units and both outputs are on the
+    device there, which is what takes the fused path: one 3 x 3 launch."""
     torch, ec = gpu
     k, m, U = 3, 2, 4096
     mat = ec.coding_matrix(k, m)
-    nunits = 4 * 1024 + 3
     n = nunits * U
     data = [oracle.splitmix_bytes(0xC0C70105 + j, n) for j in range(k)]
     pdev = [to_dev(torch, p) for p in oracle.encode(mat, k, m, data)]
     mask = 0b11100
-    with ec.Recovery(k, m, mat, 3, mask, 0, nunits - 1, pdev[0]) as r0, \
-         ec.Recovery(k, m, mat, 4, mask, 0, nunits - 1, pdev[1]) as r1:
+    other = 7 - leader  # the parity that ships its residual
+    with ec.Recovery(k, m, mat, leader, mask, 0, nunits - 1, pdev[leader - k]) as r0, \
+         ec.Recovery(k, m, mat, other, mask, 0, nunits - 1, pdev[other - k]) as r1:
         r1.add_peer(2, data[2])
         res1 = torch.empty(n, dtype=torch.uint8, device="cuda")
         ec.region_multiply(r1.residual, 1, n, res1, 0)
@@ -1544,7 +1552,14 @@ def test_recovery_finish_double_loss(gpu, oracle, outs_kind):
         res1_host = to_host(res1)
         o0 = np.zeros(n, np.uint8) if outs_kind != "device" else torch.zeros(n, dtype=torch.uint8, device="cuda")
         o1 = np.zeros(n, np.uint8) if outs_kind == "two_pageable" else torch.zeros(n, dtype=torch.uint8, device="cuda")
-        r0.finish(2, data[2], {4: res1_host}, {0: o0, 1: o1})
+        fused = leader == 4
+        units = to_dev(torch, data[2]) if fused else data[2]
+        torch.cuda.synchronize()
+        seq = ec.last_launch()["seq"]
+        r0.finish(2, units, {other: res1_host}, {0: o0, 1: o1})
+        if fused:
+            rec = ec.last_launch()
+            assert rec["seq"] == seq + 1 and (rec["nt"], rec["lt"]) == (3, 3), rec
         torch.cuda.synchronize()
     got = [x.cpu().numpy() if hasattr(x, "cpu") else x for x in (o0, o1)]
     assert np.array_equal(got[0], data[0]) and np.array_equal(got[1], data[1])
