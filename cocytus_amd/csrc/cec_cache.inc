@@ -8,6 +8,8 @@
 //   * BufCache: idle device / pinned buffers kept for reuse.  hipFree and hipHostFree
 //     wait for the device; releasing into the cache does not.  Sizes are bucketed at
 //     <= 12.5 % waste and the cache is capped; cec_cache_trim() frees it.
+//   * Buf, HalfPipe, InFlight, classify: what the ops hold the caches' buffers, their
+//     two staging halves, their queued work and their callers' pointers with.
 //   * PatternCache: coefficient tables per (device, content), LRU-bounded, uploaded
 //     asynchronously from a pinned mirror on the first caller's stream; another stream
 //     waits on the upload event (until it is known complete).  Tables used inside a
@@ -266,6 +268,156 @@ BufCache &pin_cache() {
 BufCache &map_cache() {  // pinned, mapped into the device address space, coherent
     static BufCache *c = new BufCache(kBufMapped, size_t(512) << 20);
     return *c;
+}
+
+// ---------------------------------------------------------------- holders
+// One allocation of a BufCache.  It remembers its cache, device and byte count, so the
+// release (explicit, on re-acquire, or when the holder dies) cannot disagree with the
+// acquire.  As with BufCache::release, the buffer must be idle by then.  A mapped holder
+// (map_cache()) also carries the buffer's device alias.
+class Buf {
+  public:
+    Buf() = default;
+    Buf(const Buf &) = delete;
+    Buf &operator=(const Buf &) = delete;
+    Buf &operator=(Buf &&o) noexcept {
+        if (this != &o) {
+            release();
+            cache_ = o.cache_, dev_ = o.dev_, bytes_ = o.bytes_, p_ = o.p_, alias_ = o.alias_;
+            o.p_ = o.alias_ = nullptr;
+            o.bytes_ = 0;
+        }
+        return *this;
+    }
+    ~Buf() { release(); }
+    // >= bytes from cache c on device dev (the current device); false, and empty, if out of memory
+    bool acquire(BufCache &c, int dev, size_t bytes) {
+        release();
+        if (!(p_ = c.acquire(dev, bytes))) return false;
+        cache_ = &c, dev_ = dev, bytes_ = bytes;
+        return true;
+    }
+    // ... mapped pinned, with its device alias; false, and empty, if either step fails
+    bool acquire_mapped(int dev, size_t bytes) {
+        if (acquire(map_cache(), dev, bytes) && hipHostGetDevicePointer(&alias_, p_, 0) == hipSuccess) return true;
+        (void)hipGetLastError();
+        release();
+        return false;
+    }
+    void release() {
+        if (p_) cache_->release(dev_, p_, bytes_);
+        p_ = alias_ = nullptr;
+        bytes_ = 0;
+    }
+    size_t bytes() const { return bytes_; }  // as acquired; 0 when empty
+    explicit operator bool() const { return p_ != nullptr; }
+    template <class T = uint8_t> T *get() const { return static_cast<T *>(p_); }
+    template <class T = uint8_t> T *alias() const { return static_cast<T *>(alias_); }
+
+  private:
+    BufCache *cache_ = nullptr;
+    int dev_ = -1;
+    size_t bytes_ = 0;
+    void *p_ = nullptr, *alias_ = nullptr;
+};
+
+// Two halves of a staging area with an event and a pending flag each: half h may be
+// overwritten from the host once the work recorded behind its last use has completed.
+struct HalfPipe {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool pending[2] = {false, false};
+    HalfPipe() = default;
+    HalfPipe(const HalfPipe &) = delete;
+    HalfPipe &operator=(const HalfPipe &) = delete;
+    ~HalfPipe() { destroy(); }
+    hipError_t create(unsigned flags) {  // (the events still missing)
+        for (hipEvent_t &e : ev)
+            if (!e)
+                if (hipError_t rc = hipEventCreateWithFlags(&e, flags); rc != hipSuccess) return rc;
+        return hipSuccess;
+    }
+    void destroy() {
+        for (hipEvent_t &e : ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+        forget();
+    }
+    hipError_t wait(int h) {
+        if (!pending[h]) return hipSuccess;
+        const hipError_t rc = hipEventSynchronize(ev[h]);
+        if (rc == hipSuccess) pending[h] = false;
+        return rc;
+    }
+    hipError_t record(int h, hipStream_t s) {
+        const hipError_t rc = hipEventRecord(ev[h], s);
+        if (rc == hipSuccess) pending[h] = true;
+        return rc;
+    }
+    hipError_t wait_all() {
+        const hipError_t a = wait(0), b = wait(1);
+        return a != hipSuccess ? a : b;
+    }
+    void forget() { pending[0] = pending[1] = false; }  // (the stream was synchronised)
+};
+
+// Nothing of a failed call may stay in flight: its earlier launches and copies may still
+// read the object's staging and tile lists, which the next call overwrites from the host.
+// Declared where a call starts to enqueue such work; every exit that did not dismiss()
+// it -- a failed launch, any HIP_TRY -- synchronises the stream and clears the sticky
+// error.  A success path keeps its own completion and dismisses: no second wait.
+class InFlight {
+  public:
+    explicit InFlight(hipStream_t s, HalfPipe *pipe = nullptr) : s_(s), pipe_(pipe) {}
+    InFlight(const InFlight &) = delete;
+    InFlight &operator=(const InFlight &) = delete;
+    ~InFlight() {
+        if (!armed_) return;
+        (void)hipStreamSynchronize(s_);
+        (void)hipGetLastError();
+        if (pipe_) pipe_->forget();
+    }
+    void dismiss() { armed_ = false; }
+
+  private:
+    hipStream_t s_;
+    HalfPipe *pipe_;
+    bool armed_ = true;
+};
+
+// What kind of memory p is: its device-usable address (device memory, or pinned /
+// registered / managed host memory mapped into the device address space; NULL for
+// pageable host memory), and whether the host may read it in place on return -- pinned
+// or managed memory, so a result the kernel wrote there needs the system-scope release.
+struct PtrKind {
+    void *dev = nullptr;
+    bool host = false;
+    bool known = false;  // the query succeeded
+    bool device_memory() const { return dev && !host; }
+};
+PtrKind classify(const void *p) {
+    PtrKind k;
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return k;
+    }
+    k.known = true;
+    k.host = at.type == hipMemoryTypeHost || at.type == hipMemoryTypeManaged;
+    if (k.host || at.type == hipMemoryTypeDevice) k.dev = at.devicePointer;
+    return k;
+}
+void *device_view_of(const void *p) { return classify(p).dev; }
+
+// Any of the n outputs in host memory (pinned / registered / managed): the synchronous call
+// that wrote them then waits with host_results (stream_wait).  Unknown: be safe.
+bool any_host_memory(uint8_t *const *out, int n) {
+    for (int i = 0; out && i < n; ++i) {
+        if (!out[i]) continue;
+        const PtrKind k = classify(out[i]);
+        if (!k.known || k.host) return true;
+    }
+    return false;
 }
 
 // ---------------------------------------------------------------- pattern cache

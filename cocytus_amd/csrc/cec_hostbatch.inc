@@ -1,6 +1,9 @@
 // cec_hostbatch.inc -- galois_w08_region_multiply, batched, over host memory.
-// Included by cec_runtime.hip after cec_recovery.inc (shares PackPool, stream_wait and
-// the launch internals); not a separate TU.
+// Included by cec_runtime.hip after cec_recovery.inc (shares stream_wait and the launch
+// internals); not a separate TU.  The planning below the C-ABI -- HbPiece, HbCluster,
+// MaxTree, hb_cluster_waves, radix_sort -- and PackPool / split_copy are in
+// cec_hostplan.hpp; Buf, HalfPipe and InFlight in cec_cache.inc; WaveTiles in
+// cec_runtime.hip.
 //
 // The unchanged server keeps its recovery state in host memory: one malloc'd 4 KiB
 // buffer per recovery unit (recovery.c:79), the parity arena `ecmem` (recovery.c:81),
@@ -78,241 +81,29 @@ bool host_region_find(uintptr_t a, size_t n, int dev, HostRegion *out) {
     return false;
 }
 
-enum HbKind : uint8_t { kHbXor = 0, kHbWrite = 1, kHbBase = 2 };
-
-struct HbPiece {
-    const uint8_t *src, *base;
-    uint8_t *dst;
-    uint32_t len;
-    uint8_t kind, multby;
-    int job;         // caller's job index (order)
-    int cluster;
-    int wave;
-    int pat;
-    uint64_t soff;   // byte offset in S (and B) of this round
-};
-
-struct HbCluster {
-    uintptr_t lo, hi;
-    int first, count;  // pieces [first, first + count) of the cluster-sorted order
-    bool packed;       // dst bytes staged in (some byte is read before it is written)
-    int waves;
-    uint64_t doff;
-};
-
-// Range-assign / range-max tree over compressed coordinates: the wave of a piece of a
-// cluster holding a write is 1 + the highest wave of the earlier pieces it overlaps.
-class MaxTree {
-  public:
-    explicit MaxTree(size_t n) : n_(std::max<size_t>(n, 1)), mx_(4 * n_, -1), lz_(4 * n_, -2) {}
-    int query(size_t l, size_t r) { return q(1, 0, n_, l, r); }
-    void assign(size_t l, size_t r, int v) { a(1, 0, n_, l, r, v); }
-
-  private:
-    void push(size_t x) {
-        if (lz_[x] == -2) return;
-        for (size_t c : {2 * x, 2 * x + 1}) mx_[c] = lz_[c] = lz_[x];
-        lz_[x] = -2;
-    }
-    int q(size_t x, size_t lo, size_t hi, size_t l, size_t r) {
-        if (r <= lo || hi <= l) return -1;
-        if (l <= lo && hi <= r) return mx_[x];
-        push(x);
-        const size_t mid = (lo + hi) / 2;
-        return std::max(q(2 * x, lo, mid, l, r), q(2 * x + 1, mid, hi, l, r));
-    }
-    void a(size_t x, size_t lo, size_t hi, size_t l, size_t r, int v) {
-        if (r <= lo || hi <= l) return;
-        if (l <= lo && hi <= r) {
-            mx_[x] = lz_[x] = v;
-            return;
-        }
-        push(x);
-        const size_t mid = (lo + hi) / 2;
-        a(2 * x, lo, mid, l, r, v);
-        a(2 * x + 1, mid, hi, l, r, v);
-        mx_[x] = std::max(mx_[2 * x], mx_[2 * x + 1]);
-    }
-    size_t n_;
-    std::vector<int> mx_, lz_;
-};
-
-// Waves of one cluster's pieces (ids = indices into pc, in cluster-sorted order).
-// Returns the number of waves; sets packed (some byte is read before any write).
-int hb_cluster_waves(std::vector<HbPiece> &pc, const int *ids, int count, bool *packed) {
-    if (count == 1) {
-        pc[ids[0]].wave = 0;
-        *packed = pc[ids[0]].kind == kHbXor;
-        return 1;
-    }
-    bool writes = false;
-    for (int i = 0; i < count; ++i) writes |= pc[ids[i]].kind != kHbXor;
-    *packed = true;  // (a multi-piece cluster: conservatively staged in)
-    if (!writes) {
-        // greedy colouring over start-sorted pieces (ids are sorted by dst start)
-        std::vector<std::pair<uintptr_t, int>> open;  // (end, wave), min-heap on end
-        std::vector<int> free_w;
-        int nw = 0;
-        auto cmp = [](const std::pair<uintptr_t, int> &a, const std::pair<uintptr_t, int> &b) {
-            return a.first > b.first;
-        };
-        for (int i = 0; i < count; ++i) {
-            HbPiece &p = pc[ids[i]];
-            const uintptr_t lo = reinterpret_cast<uintptr_t>(p.dst);
-            while (!open.empty() && open.front().first <= lo) {
-                free_w.push_back(open.front().second);
-                std::pop_heap(open.begin(), open.end(), cmp);
-                open.pop_back();
-            }
-            int w;
-            if (!free_w.empty()) {
-                auto it = std::min_element(free_w.begin(), free_w.end());
-                w = *it;
-                free_w.erase(it);
-            } else {
-                w = nw++;
-            }
-            p.wave = w;
-            open.emplace_back(lo + p.len, w);
-            std::push_heap(open.begin(), open.end(), cmp);
-        }
-        return std::max(nw, 1);
-    }
-    // job order: wave = 1 + the highest wave among earlier overlapping pieces
-    std::vector<uintptr_t> xs;
-    xs.reserve(2 * count);
-    for (int i = 0; i < count; ++i) {
-        const uintptr_t lo = reinterpret_cast<uintptr_t>(pc[ids[i]].dst);
-        xs.push_back(lo);
-        xs.push_back(lo + pc[ids[i]].len);
-    }
-    std::sort(xs.begin(), xs.end());
-    xs.erase(std::unique(xs.begin(), xs.end()), xs.end());
-    std::vector<int> ord(ids, ids + count);
-    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return pc[a].job < pc[b].job; });
-    MaxTree tree(xs.size());
-    int nw = 0;
-    for (int id : ord) {
-        HbPiece &p = pc[id];
-        const uintptr_t lo = reinterpret_cast<uintptr_t>(p.dst);
-        const size_t l = std::lower_bound(xs.begin(), xs.end(), lo) - xs.begin();
-        const size_t r = std::lower_bound(xs.begin(), xs.end(), lo + p.len) - xs.begin();
-        p.wave = tree.query(l, r) + 1;
-        tree.assign(l, r, p.wave);
-        nw = std::max(nw, p.wave + 1);
-    }
-    return nw;
-}
-
-// (key, index) pairs sorted by key: LSD radix sort, 11-bit digits, digits on which every
-// key agrees skipped (host addresses of one batch differ in their low ~40 bits: <= 4 passes).
-void hb_radix_sort(std::vector<std::pair<uint64_t, int>> &a) {
-    if (a.size() < 1024) {  // (a radix pass touches 2,049 counters: small batches sort faster)
-        std::sort(a.begin(), a.end());
-        return;
-    }
-    uint64_t orv = 0, andv = ~0ull;
-    for (const auto &x : a) {
-        orv |= x.first;
-        andv &= x.first;
-    }
-    const uint64_t varies = orv ^ andv;
-    std::vector<std::pair<uint64_t, int>> b(a.size());
-    for (int shift = 0; shift < 64; shift += 11) {
-        if (((varies >> shift) & 0x7FF) == 0) continue;
-        size_t cnt[2049] = {};
-        for (const auto &x : a) ++cnt[((x.first >> shift) & 0x7FF) + 1];
-        for (int d = 0; d < 2048; ++d) cnt[d + 1] += cnt[d];
-        for (const auto &x : a) b[cnt[(x.first >> shift) & 0x7FF]++] = x;  // stable
-        a.swap(b);
-    }
-}
-
-struct HbCopy {
-    uint8_t *dst;
-    const uint8_t *src;
-    size_t len;
-};
-
-// Copies through the pack pool: thread t takes bytes [t*B/T, (t+1)*B/T) of the list.
-void hb_copy(PackPool *pool, const std::vector<HbCopy> &items) {
-    size_t total = 0;
-    for (const HbCopy &c : items) total += c.len;
-    if (!pool || pool->size() == 1 || total < kHbParallelCopy) {
-        for (const HbCopy &c : items) memcpy(c.dst, c.src, c.len);
-        return;
-    }
-    std::vector<size_t> prefix(items.size() + 1, 0);
-    for (size_t i = 0; i < items.size(); ++i) prefix[i + 1] = prefix[i] + items[i].len;
-    const int T = pool->size();
-    pool->run([&](int t) {
-        const size_t lo = total * t / T, hi = total * (t + 1) / T;
-        if (lo >= hi) return;
-        size_t i = std::upper_bound(prefix.begin(), prefix.end(), lo) - prefix.begin() - 1;
-        for (size_t pos = lo; pos < hi && i < items.size(); ++i) {
-            const HbCopy &c = items[i];
-            const size_t a = pos - prefix[i], b = std::min(c.len, hi - prefix[i]);
-            if (b > a) memcpy(c.dst + a, c.src + a, b - a);
-            pos = prefix[i] + b;
-        }
-    });
-}
-
 struct HostBatchCtx {  // per thread and device
     int device = -1;
-    uint8_t *stage = nullptr;  // mapped pinned
-    uint8_t *stage_dev = nullptr;
-    size_t cap = 0;
-    Tile *h_tiles = nullptr, *d_tiles = nullptr;
-    size_t tile_cap = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};  // round completion per staging half (pipelined batches)
+    Buf stage;  // mapped pinned
+    // the tile list lives in mapped pinned memory too: the kernel's scalar loads read it
+    // over PCIe, so a round needs no copy of it (one DMA set-up less per call)
+    Buf tiles;
+    HalfPipe pipe;  // round completion per staging half (pipelined batches)
     std::unique_ptr<PackPool> pool;
     int last_launches = 0, last_rounds = 0, last_in_place = 0;
     double t_plan = 0, t_pack = 0, t_gpu = 0, t_unpack = 0;  // last call, microseconds
-    ~HostBatchCtx() {
-        release();
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    void release() {  // (idle: every call completed before returning)
-        map_cache().release(device, stage, cap);
-        map_cache().release(device, h_tiles, tile_cap * sizeof(Tile));
-        stage = stage_dev = nullptr;
-        h_tiles = d_tiles = nullptr;
-        cap = tile_cap = 0;
-    }
-    int reserve(int dev, size_t bytes, size_t tiles) {
+    // (buffers are idle whenever they are released: every call completed before returning)
+    int reserve(int dev, size_t bytes, size_t n_tiles) {
         if (device != dev) {  // (events and mapped addresses are per device)
-            release();
-            for (hipEvent_t &e : ev)
-                if (e) {
-                    (void)hipEventDestroy(e);
-                    e = nullptr;
-                }
+            stage.release();
+            tiles.release();
+            pipe.destroy();
             device = dev;
         }
-        if (cap < bytes) {
-            map_cache().release(device, stage, cap);
-            stage = stage_dev = nullptr;
-            cap = 0;
-            const size_t want = std::max(bytes, kHbStage);
-            stage = static_cast<uint8_t *>(map_cache().acquire(dev, want));
-            if (!stage) return fail(CEC_ENOMEM, "cec_region_multiply_batch: %zu bytes of mapped staging", want);
-            cap = want;
-            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&stage_dev), stage, 0));
-        }
-        if (tile_cap < tiles) {
-            // the tile list lives in mapped pinned memory too: the kernel's scalar loads read
-            // it over PCIe, so a round needs no copy of it (one DMA set-up less per call)
-            map_cache().release(device, h_tiles, tile_cap * sizeof(Tile));
-            h_tiles = d_tiles = nullptr;
-            tile_cap = 0;
-            const size_t want = std::max(tiles, kHbStage / kTile * 2 + 1024);
-            h_tiles = static_cast<Tile *>(map_cache().acquire(dev, want * sizeof(Tile)));
-            if (!h_tiles) return fail(CEC_ENOMEM, "cec_region_multiply_batch: tile list of %zu", want);
-            tile_cap = want;
-            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&d_tiles), h_tiles, 0));
-        }
+        if (stage.bytes() < bytes && !stage.acquire_mapped(dev, std::max(bytes, kHbStage)))
+            return fail(CEC_ENOMEM, "cec_region_multiply_batch: %zu bytes of mapped staging", bytes);
+        if (tiles.bytes() < n_tiles * sizeof(Tile) &&
+            !tiles.acquire_mapped(dev, std::max(n_tiles, kHbStage / kTile * 2 + 1024) * sizeof(Tile)))
+            return fail(CEC_ENOMEM, "cec_region_multiply_batch: tile list of %zu", n_tiles);
         if (!pool) pool.reset(new PackPool(pack_threads() - 1));
         return CEC_OK;
     }
@@ -388,7 +179,7 @@ CEC_API int cec_region_multiply_batch(const cec_region_job *jobs, int n, void *s
     {
         std::vector<std::pair<uint64_t, int>> key(pc.size());
         for (size_t i = 0; i < pc.size(); ++i) key[i] = {reinterpret_cast<uintptr_t>(pc[i].dst), static_cast<int>(i)};
-        hb_radix_sort(key);
+        radix_sort(key);
         for (size_t i = 0; i < pc.size(); ++i) ids[i] = key[i].second;
     }
     std::vector<HbCluster> cl;
@@ -414,7 +205,7 @@ CEC_API int cec_region_multiply_batch(const cec_region_job *jobs, int n, void *s
             rd.emplace_back(reinterpret_cast<uintptr_t>(pc[i].src), static_cast<int>(2 * i));
             if (pc[i].base) rd.emplace_back(reinterpret_cast<uintptr_t>(pc[i].base), static_cast<int>(2 * i + 1));
         }
-        hb_radix_sort(rd);
+        radix_sort(rd);
         size_t c = 0;
         for (const auto &x : rd) {
             const HbPiece &p = pc[x.second / 2];
@@ -535,15 +326,12 @@ CEC_API int cec_region_multiply_batch(const cec_region_job *jobs, int n, void *s
     const uint64_t half = r4k(piped ? std::max<uint64_t>(max_half, half_cap) : max_half);
     const uint64_t tile_half = std::max<uint64_t>(max_tiles, piped ? tile_cap : 0);
     if (int r = hb.reserve(dev, piped ? 2 * half : half, piped ? 2 * tile_half : tile_half)) return r;
-    if (piped) {
-        for (int h = 0; h < 2; ++h)
-            if (!hb.ev[h]) HIP_TRY(hipEventCreateWithFlags(&hb.ev[h], hipEventDisableTiming | hipEventReleaseToSystem));
-    }
-    std::vector<HbCopy> in, out[2];
+    if (piped) HIP_TRY(hb.pipe.create(hipEventDisableTiming | hipEventReleaseToSystem));
+    std::vector<CopyItem> in, out[2];
     // lay round r out in half h, pack it, launch it (and record its event when piped)
     auto issue = [&](const Round &rd, int h) -> int {
-        uint8_t *stage = hb.stage + h * half, *stage_dev = hb.stage_dev + h * half;
-        Tile *ht = hb.h_tiles + h * tile_half, *dt = hb.d_tiles + h * tile_half;
+        uint8_t *stage = hb.stage.get() + h * half, *stage_dev = hb.stage.alias() + h * half;
+        Tile *ht = hb.tiles.get<Tile>() + h * tile_half, *dt = hb.tiles.alias<Tile>() + h * tile_half;
         if ((reinterpret_cast<uintptr_t>(stage) | reinterpret_cast<uintptr_t>(stage_dev)) & 15)
             return fail(CEC_EINVAL, "cec_region_multiply_batch: staging half %d is not 16-B aligned", h);
         in.clear();
@@ -555,85 +343,79 @@ CEC_API int cec_region_multiply_batch(const cec_region_job *jobs, int n, void *s
             dcur = a16(dcur, c.lo);
             c.doff = dcur;
             dcur += c.hi - c.lo;
-            if (c.packed) in.push_back(HbCopy{stage + c.doff, reinterpret_cast<const uint8_t *>(c.lo), c.hi - c.lo});
-            out[h].push_back(HbCopy{reinterpret_cast<uint8_t *>(c.lo), stage + c.doff, c.hi - c.lo});
+            if (c.packed) in.push_back(CopyItem{stage + c.doff, reinterpret_cast<const uint8_t *>(c.lo), c.hi - c.lo});
+            out[h].push_back(CopyItem{reinterpret_cast<uint8_t *>(c.lo), stage + c.doff, c.hi - c.lo});
             max_wave = std::max(max_wave, c.waves);
             for (int x = 0; x < c.count; ++x) {
                 HbPiece &p = pc[ids[c.first + x]];
                 if (rd.in_place) {  // S at D's offset; B (if any) read in place at src_off
-                    in.push_back(HbCopy{stage + rd.dseg + c.doff, p.src, p.len});
+                    in.push_back(CopyItem{stage + rd.dseg + c.doff, p.src, p.len});
                     p.soff = p.base ? reinterpret_cast<uintptr_t>(p.base) - rd.reg.lo : 0;
                     continue;
                 }
                 scur = a16(scur, reinterpret_cast<uintptr_t>(p.dst));
                 p.soff = scur;
                 scur += p.len;
-                in.push_back(HbCopy{stage + rd.dseg + p.soff, p.src, p.len});
-                if (p.kind == kHbBase) in.push_back(HbCopy{stage + rd.dseg + rd.sseg + p.soff, p.base, p.len});
+                in.push_back(CopyItem{stage + rd.dseg + p.soff, p.src, p.len});
+                if (p.kind == kHbBase) in.push_back(CopyItem{stage + rd.dseg + rd.sseg + p.soff, p.base, p.len});
             }
         }
-        std::vector<size_t> span(max_wave + 1, 0);  // tiles of wave w: [span[w], span[w+1])
+        WaveTiles wt(ht);
         {
             std::vector<std::vector<int>> by_wave(max_wave);
             for (size_t ci = rd.next; ci < rd.end; ++ci)
                 for (int x = 0; x < cl[ci].count; ++x) by_wave[pc[ids[cl[ci].first + x]].wave].push_back(ids[cl[ci].first + x]);
-            size_t nt = 0;
             for (int w = 0; w < max_wave; ++w) {
-                span[w] = nt;
+                wt.begin_wave();
                 for (int id : by_wave[w]) {
                     const HbPiece &p = pc[id];
                     const HbCluster &c = cl[p.cluster];
-                    nt += append_tiles(ht + nt, c.doff + (reinterpret_cast<uintptr_t>(p.dst) - c.lo), p.soff, p.len,
-                                       static_cast<uint32_t>(p.pat));
+                    wt.add(c.doff + (reinterpret_cast<uintptr_t>(p.dst) - c.lo), p.soff, p.len, static_cast<uint32_t>(p.pat));
                 }
             }
-            span[max_wave] = nt;
         }
         const clk::time_point t0 = clk::now();
-        hb_copy(hb.pool.get(), in);
+        split_copy(hb.pool.get(), in, kHbParallelCopy);
         hb.t_pack += us(t0, clk::now());
         const HbStreams hs(stage_dev, stage_dev + rd.dseg,  // D; S (by tile.src_off; in place: by tile.off)
                            rd.in_place ? rd.reg.alias       // B in place
                                        : rd.any_base ? stage_dev + rd.dseg + rd.sseg : stage_dev + rd.dseg);  // B staged
         for (int w = 0; w < max_wave; ++w) {
-            if (span[w + 1] == span[w]) continue;
-            const TileSource wave = TileSource::window(dt + span[w], ht + span[w], span[w + 1] - span[w]);
+            const TileSource wave = wt.window(w, dt);
+            if (!wave.n_tiles) continue;
             if (int r = run_combos(dev, hs.st, rd.in_place ? combos_ip : combos, wave, s)) return r;
             ++hb.last_launches;
             hb.last_in_place += rd.in_place;
         }
         // (an event's completion carries the system-scope release of the kernels' writes
         // into the mapped staging: the host reads it after hipEventSynchronize)
-        if (piped) HIP_TRY(hipEventRecord(hb.ev[h], s));
+        if (piped) HIP_TRY(hb.pipe.record(h, s));
         ++hb.last_rounds;
         return CEC_OK;
     };
     auto drain = [&](int h) -> int {  // wait for half h's round, then copy its clusters out
         const clk::time_point t0 = clk::now();
         if (piped) {
-            HIP_TRY(hipEventSynchronize(hb.ev[h]));
+            HIP_TRY(hb.pipe.wait(h));
         } else if (int r = stream_wait(s, true)) {  // one round: the low-latency completion
             return r;
         }
         const clk::time_point t1 = clk::now();
-        hb_copy(hb.pool.get(), out[h]);
+        split_copy(hb.pool.get(), out[h], kHbParallelCopy);
         hb.t_gpu += us(t0, t1);
         hb.t_unpack += us(t1, clk::now());
         return CEC_OK;
     };
     // on a failure, nothing of this call may stay in flight: the staging is the thread's,
     // and its next call packs into it
-    auto bail = [&](int rc) {
-        (void)hipStreamSynchronize(s);
-        (void)hipGetLastError();
-        return rc;
-    };
+    InFlight guard(s, &hb.pipe);
     for (size_t r = 0; r < rounds.size(); ++r) {
         const int h = static_cast<int>(r & 1);
-        if (int rc = issue(rounds[r], h)) return bail(rc);
+        if (int rc = issue(rounds[r], h)) return rc;
         if (r > 0)
-            if (int rc = drain(h ^ 1)) return bail(rc);
+            if (int rc = drain(h ^ 1)) return rc;
     }
-    if (int rc = drain(static_cast<int>((rounds.size() - 1) & 1))) return bail(rc);
+    if (int rc = drain(static_cast<int>((rounds.size() - 1) & 1))) return rc;
+    guard.dismiss();
     return CEC_OK;
 }

@@ -1,5 +1,8 @@
 // cec_pool.inc -- background recovery of many small unit ranges (SURVEY §8f rank 2).
-// Included by cec_runtime.hip after cec_recovery.inc; not a separate TU.
+// Included by cec_runtime.hip after cec_recovery.inc; not a separate TU.  Every buffer
+// is a Buf (cec_cache.inc); fold_updates takes its waves from colour_intervals
+// (cec_hostplan.hpp), its launch windows from WaveTiles (cec_runtime.hip) and its
+// failure guard from InFlight (cec_cache.inc).
 //
 // The idle recoverer (idle_event_handler, memcached.c:5712-5734) issues one 4 KiB unit
 // per request (do_recovery(NULL, s, s)) with up to TOO_MANY_RECOVERY = 85 in flight
@@ -44,13 +47,11 @@ struct PoolTables {
     std::vector<uint8_t> rows;  // LDS engine product rows (pattern lds_row_base indexes these)
     size_t cap_pats = 0, cap_rows = 0;        // device blob capacity
     size_t synced_pats = 0, synced_rows = 0;  // prefix already uploaded
-    uint8_t *d = nullptr, *h = nullptr;       // device blob, pinned mirror
+    Buf d, h;                                 // device blob, pinned mirror
 
-    size_t bytes() const { return cap_pats * sizeof(Pattern) + cap_rows; }
     void release() {
-        if (d) dev_cache().release(dev, d, bytes());
-        if (h) pin_cache().release(dev, h, bytes());
-        d = h = nullptr;
+        d.release();
+        h.release();
         cap_pats = cap_rows = synced_pats = synced_rows = 0;
     }
     void reset(int dev_, int engine_) {  // (idle: see above)
@@ -66,30 +67,26 @@ struct PoolTables {
             const size_t np = std::max<size_t>({16, 2 * cap_pats, pats.size()});
             const size_t nr = std::max<size_t>({4096, 2 * cap_rows, (rows.size() + 4095) & ~size_t(4095)});
             const size_t nb = np * sizeof(Pattern) + nr;
-            uint8_t *nd = static_cast<uint8_t *>(dev_cache().acquire(dev, nb));
-            uint8_t *nh = static_cast<uint8_t *>(pin_cache().acquire(dev, nb));
-            if (!nd || !nh) {
-                if (nd) dev_cache().release(dev, nd, nb);
-                if (nh) pin_cache().release(dev, nh, nb);
+            Buf nd, nh;
+            if (!nd.acquire(dev_cache(), dev, nb) || !nh.acquire(pin_cache(), dev, nb))
                 return fail(CEC_ENOMEM, "recovery pool: %zu bytes of coefficient tables", nb);
-            }
             release();
-            d = nd;
-            h = nh;
+            d = std::move(nd);
+            h = std::move(nh);
             cap_pats = np;
             cap_rows = nr;
         }
         const size_t rbase = cap_pats * sizeof(Pattern);
         if (synced_pats < pats.size()) {
             const size_t o = synced_pats * sizeof(Pattern), n = (pats.size() - synced_pats) * sizeof(Pattern);
-            memcpy(h + o, pats.data() + synced_pats, n);
-            HIP_TRY(hipMemcpyAsync(d + o, h + o, n, hipMemcpyHostToDevice, s));
+            memcpy(h.get() + o, pats.data() + synced_pats, n);
+            HIP_TRY(hipMemcpyAsync(d.get() + o, h.get() + o, n, hipMemcpyHostToDevice, s));
             synced_pats = pats.size();
         }
         if (synced_rows < rows.size()) {
             const size_t o = rbase + synced_rows, n = rows.size() - synced_rows;
-            memcpy(h + o, rows.data() + synced_rows, n);
-            HIP_TRY(hipMemcpyAsync(d + o, h + o, n, hipMemcpyHostToDevice, s));
+            memcpy(h.get() + o, rows.data() + synced_rows, n);
+            HIP_TRY(hipMemcpyAsync(d.get() + o, h.get() + o, n, hipMemcpyHostToDevice, s));
             synced_rows = rows.size();
         }
         return CEC_OK;
@@ -103,15 +100,13 @@ struct cec_recovery_pool {
     Code code;  // over `matrix`
     const uint8_t *parity = nullptr;  // this parity's arena (device)
     int capacity = 0;                 // units
-    uint8_t *residual = nullptr;      // device, capacity * kTile
-    uint8_t *q_host[CEC_MAX_K] = {};  // per data lid: pinned, mapped, capacity * kTile
-    uint8_t *q_dev[CEC_MAX_K] = {};
+    Buf residual;      // device, capacity * kTile
+    Buf q[CEC_MAX_K];  // per data lid: pinned, mapped, capacity * kTile
     // capacity tiles (one flush / solve), mapped pinned: the kernel reads them in place over
-    // PCIe (no upload ahead of each launch); d_tiles is h_tiles' device alias
-    Tile *h_tiles = nullptr, *d_tiles = nullptr;
-    uint8_t *diff_host = nullptr, *diff_dev = nullptr;  // pinned mapped staging for diffs
-    size_t diff_cap = 0;
-    uint8_t *out_host = nullptr, *out_dev = nullptr;  // mapped pinned, capacity * kTile (_host solves)
+    // PCIe (no upload ahead of each launch), through the buffer's device alias
+    Buf tiles;
+    Buf diff;  // pinned mapped staging for diffs
+    Buf out;   // mapped pinned, capacity * kTile (_host solves, on first use)
     struct Req {
         bool used = false;
         uint32_t mask = 0;
@@ -139,14 +134,7 @@ struct cec_recovery_pool {
 CEC_API int cec_recovery_pool_destroy(cec_recovery_pool *p) {
     if (!p) return CEC_OK;
     (void)p->uses.wait(p->device);  // the pool's own work, not the device
-    const size_t bytes = static_cast<size_t>(p->capacity) * kTile;
-    dev_cache().release(p->device, p->residual, bytes);
-    for (uint8_t *q : p->q_host) map_cache().release(p->device, q, bytes);
-    map_cache().release(p->device, p->h_tiles, p->capacity * sizeof(Tile));
-    map_cache().release(p->device, p->diff_host, p->diff_cap);
-    map_cache().release(p->device, p->out_host, bytes);
-    p->tables.release();
-    delete p;
+    delete p;                       // (its buffers go back to the caches)
     return CEC_OK;
 }
 
@@ -176,17 +164,9 @@ CEC_API int cec_recovery_pool_create(cec_recovery_pool **out, int k, int m, cons
     p->parity = parity_arena;
     p->capacity = capacity_units;
     const size_t bytes = static_cast<size_t>(capacity_units) * kTile;
-    p->residual = static_cast<uint8_t *>(dev_cache().acquire(dev, bytes));
-    p->h_tiles = static_cast<Tile *>(map_cache().acquire(dev, capacity_units * sizeof(Tile)));
-    bool ok = p->residual && p->h_tiles &&
-              hipHostGetDevicePointer(reinterpret_cast<void **>(&p->d_tiles), p->h_tiles, 0) == hipSuccess;
-    for (int j = 0; j < k && ok; ++j) {
-        p->q_host[j] = static_cast<uint8_t *>(map_cache().acquire(dev, bytes));
-        ok = p->q_host[j] &&
-             hipHostGetDevicePointer(reinterpret_cast<void **>(&p->q_dev[j]), p->q_host[j], 0) == hipSuccess;
-    }
+    bool ok = p->residual.acquire(dev_cache(), dev, bytes) && p->tiles.acquire_mapped(dev, capacity_units * sizeof(Tile));
+    for (int j = 0; j < k && ok; ++j) ok = p->q[j].acquire_mapped(dev, bytes);
     if (!ok) {
-        (void)hipGetLastError();
         cec_recovery_pool_destroy(p);
         return fail(CEC_ENOMEM, "cec_recovery_pool_create: %d units of residual and staging", capacity_units);
     }
@@ -250,14 +230,15 @@ CEC_API int cec_recovery_pool_add_peer(cec_recovery_pool *p, int id, int peer, c
     if (r->contributed & (1u << peer))
         return fail(CEC_EINVAL, "cec_recovery_pool_add_peer: peer %d already applied (recovery.c:75)", peer);
     const size_t off = static_cast<size_t>(r->slot) * kTile, len = static_cast<size_t>(r->nunits) * kTile;
-    if (units == p->q_host[peer] + off) {
+    uint8_t *const q = p->q[peer].get() + off;
+    if (units == q) {
         // received in place (cec_recovery_pool_staging): nothing to copy
     } else if (const void *dv = device_view_of(units)) {  // device-resident reply: copy on the device
         int dev;
         if (int rc = current_device(&dev)) return rc;
-        HIP_TRY(hipMemcpy(p->q_host[peer] + off, dv, len, hipMemcpyDefault));
+        HIP_TRY(hipMemcpy(q, dv, len, hipMemcpyDefault));
     } else {
-        memcpy(p->q_host[peer] + off, units, len);
+        memcpy(q, units, len);
     }
     if (!r->touched) {
         r->touched = true;
@@ -299,7 +280,7 @@ CEC_API uint8_t *cec_recovery_pool_staging(cec_recovery_pool *p, int id, int pee
     cec_recovery_pool::Req *r = pool_req(p, id);
     if (!r || peer < 0 || peer >= p->code.k) return nullptr;
     if (len) *len = static_cast<size_t>(r->nunits) * kTile;
-    return p->q_host[peer] + static_cast<size_t>(r->slot) * kTile;
+    return p->q[peer].get() + static_cast<size_t>(r->slot) * kTile;
 }
 
 // Fold every queued reply in one launch.  With `out` (k arenas by data lid), a request
@@ -307,16 +288,9 @@ CEC_API uint8_t *cec_recovery_pool_staging(cec_recovery_pool *p, int id, int pee
 // the same pass: out[lost][off] = inv * R'[slot], from the same inputs (exact in GF(2^8),
 // as cec_recovery_finish).  Returns the requests folded; *solved gets those solved.
 static int pool_out_host(cec_recovery_pool *p) {  // the _host solves' output, on first use
-    if (p->out_host) return CEC_OK;
     const size_t bytes = static_cast<size_t>(p->capacity) * kTile;
-    p->out_host = static_cast<uint8_t *>(map_cache().acquire(p->device, bytes));
-    if (!p->out_host ||
-        hipHostGetDevicePointer(reinterpret_cast<void **>(&p->out_dev), p->out_host, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        map_cache().release(p->device, p->out_host, bytes);
-        p->out_host = p->out_dev = nullptr;
+    if (!p->out && !p->out.acquire_mapped(p->device, bytes))
         return fail(CEC_ENOMEM, "recovery pool: %zu bytes of host output", bytes);
-    }
     return CEC_OK;
 }
 
@@ -327,10 +301,10 @@ struct FlushStreams {
     Streams st;
     int parity, residual, q[CEC_MAX_K], out[CEC_MAX_K], out_host;
     FlushStreams(const cec_recovery_pool *p, uint8_t *const *o, bool to_host)
-        : parity(st.add(p->parity)), residual(st.add(p->residual)) {
-        for (int j = 0; j < p->code.k; ++j) q[j] = st.add(p->q_dev[j]);
+        : parity(st.add(p->parity)), residual(st.add(p->residual.get())) {
+        for (int j = 0; j < p->code.k; ++j) q[j] = st.add(p->q[j].alias());
         for (int j = 0; j < p->code.k; ++j) out[j] = st.add(o ? o[j] : nullptr);
-        out_host = st.add(to_host ? p->out_dev : nullptr);
+        out_host = st.add(to_host ? p->out.alias() : nullptr);
     }
 };
 
@@ -344,16 +318,8 @@ static int pool_single_loss(const cec_recovery_pool *p, uint32_t mask) {
 // The pool's mapped diff staging, grown to hold `len` bytes (idle: every earlier call
 // completed before returning).
 static int pool_diff_staging(cec_recovery_pool *p, size_t len, const char *op) {
-    if (p->diff_cap >= len) return CEC_OK;
-    map_cache().release(p->device, p->diff_host, p->diff_cap);
-    p->diff_host = p->diff_dev = nullptr;
-    p->diff_cap = std::max<size_t>(len, size_t(1) << 20);
-    p->diff_host = static_cast<uint8_t *>(map_cache().acquire(p->device, p->diff_cap));
-    if (!p->diff_host) {
-        p->diff_cap = 0;
+    if (p->diff.bytes() < len && !p->diff.acquire_mapped(p->device, std::max<size_t>(len, size_t(1) << 20)))
         return fail(CEC_ENOMEM, "%s: %zu bytes of diff staging", op, len);
-    }
-    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&p->diff_dev), p->diff_host, 0));
     return CEC_OK;
 }
 
@@ -412,7 +378,7 @@ static int pool_flush(cec_recovery_pool *p, uint8_t *const *out, bool to_host, v
         }
         used.resize(p->tables.pats.size(), 0);
         used[it->second] = 1;
-        nt += append_tiles(p->h_tiles + nt, static_cast<uint64_t>(r.ub) * kTile,
+        nt += append_tiles(p->tiles.get<Tile>() + nt, static_cast<uint64_t>(r.ub) * kTile,
                            static_cast<uint64_t>(r.slot) * kTile, static_cast<uint32_t>(r.nunits) * kTile,
                            static_cast<uint32_t>(it->second));
         if (lost >= 0) {
@@ -424,9 +390,9 @@ static int pool_flush(cec_recovery_pool *p, uint8_t *const *out, bool to_host, v
     used.resize(p->tables.pats.size(), 0);
     if (int rc = p->tables.sync(s)) return rc;
     // (the pool's tile buffer: whole 4 KiB units on 4 KiB offsets)
-    if (int rc = launch_combine(dev, fs.st, Tables{p->tables.d, p->tables.cap_pats, p->tables.pats.data(), &used},
+    if (int rc = launch_combine(dev, fs.st, Tables{p->tables.d.get(), p->tables.cap_pats, p->tables.pats.data(), &used},
                                 launch_shape(p->tables.pats, &used), engine == CEC_ENGINE_LDS,
-                                TileSource::whole_units(p->d_tiles, nt), s))
+                                TileSource::whole_units(p->tiles.alias<Tile>(), nt), s))
         return rc;
     HIP_TRY(hipGetLastError());
     // tile buffer and staging reusable; rebuilt shards visible if out is host memory
@@ -465,7 +431,7 @@ CEC_API const uint8_t *cec_recovery_pool_output(const cec_recovery_pool *p, int 
     const cec_recovery_pool::Req &r = p->reqs[id];
     if (!r.solved || !r.solved_host) return nullptr;
     if (len) *len = static_cast<size_t>(r.nunits) * kTile;
-    return p->out_host + static_cast<size_t>(r.slot) * kTile;
+    return p->out.get() + static_cast<size_t>(r.slot) * kTile;
 }
 
 CEC_API int cec_recovery_pool_solved(const cec_recovery_pool *p, int id) {
@@ -504,7 +470,7 @@ CEC_API int cec_recovery_pool_fold_update(cec_recovery_pool *p, int peer, uint64
         const uint64_t lo = std::max(addr, base), hi = std::min(addr + len, end);
         if (lo >= hi) continue;
         r.solved = r.solved_host = false;  // (a lost lid's diff after the solve: R moved on)
-        nt += append_tiles(p->h_tiles + nt, static_cast<uint64_t>(r.slot) * kTile + (lo - base), lo - addr,
+        nt += append_tiles(p->tiles.get<Tile>() + nt, static_cast<uint64_t>(r.slot) * kTile + (lo - base), lo - addr,
                            static_cast<uint32_t>(hi - lo), 0);
         units += static_cast<int>((hi - 1) / kTile - lo / kTile + 1);
     }
@@ -512,11 +478,12 @@ CEC_API int cec_recovery_pool_fold_update(cec_recovery_pool *p, int peer, uint64
     const uint8_t *d = static_cast<const uint8_t *>(device_view_of(diff));
     if (!d) {  // pageable diff: through the pool's mapped pinned staging (zero-copy)
         if (int rc = pool_diff_staging(p, len, "cec_recovery_pool_fold_update")) return rc;
-        memcpy(p->diff_host, diff, len);
-        d = p->diff_dev;
+        memcpy(p->diff.get(), diff, len);
+        d = p->diff.alias();
     }
-    const Fold f = fold(p->code, p->lid_self, d, p->residual, peer);  // recovery.c:123
-    if (int rc = run_combos(dev, f.st, f.combos, TileSource::window(p->d_tiles, p->h_tiles, nt), s)) return rc;
+    const Fold f = fold(p->code, p->lid_self, d, p->residual.get(), peer);  // recovery.c:123
+    if (int rc = run_combos(dev, f.st, f.combos, TileSource::window(p->tiles.alias<Tile>(), p->tiles.get<Tile>(), nt), s))
+        return rc;
     if (int rc = stream_wait(s, false)) return rc;  // (the residual is in HBM)
     return units;
 }
@@ -525,8 +492,8 @@ CEC_API int cec_recovery_pool_fold_update(cec_recovery_pool *p, int peer, uint64
 // lids): the same rule as cec_recovery_pool_fold_update per update, every fold of the
 // window in one upload and one launch per overlap wave.  The pieces are packed into the
 // pool's mapped diff staging; pieces of different updates that meet in R go to separate
-// waves (first fit over the pieces sorted by R offset: XOR folds commute, so any order
-// within a byte gives the sequential bytes).  units[i] (optional) = the units update i
+// waves (colour_intervals over the tiles sorted by R offset: XOR folds commute, so any
+// order within a byte gives the sequential bytes).  units[i] (optional) = the units update i
 // folded, as cec_recovery_pool_fold_update returns them.
 CEC_API int cec_recovery_pool_fold_updates(cec_recovery_pool *p, const cec_host_update *u, int n, int *units,
                                            void *stream) {
@@ -595,7 +562,7 @@ CEC_API int cec_recovery_pool_fold_updates(cec_recovery_pool *p, const cec_host_
     tiles.reserve(pieces.size() + staged / kTile + 1);
     size_t so = 0;
     for (const Piece &pc : pieces) {
-        memcpy(p->diff_host + so, static_cast<const uint8_t *>(u[pc.upd].buf) + pc.d_off, pc.len);
+        memcpy(p->diff.get() + so, static_cast<const uint8_t *>(u[pc.upd].buf) + pc.d_off, pc.len);
         Tile tmp[33];
         for (uint32_t o = 0; o < pc.len;) {  // <= 32 units per step: <= 33 tiles (append_tiles' split)
             const uint32_t step = std::min<uint32_t>(pc.len - o, 32 * kTile);
@@ -605,52 +572,40 @@ CEC_API int cec_recovery_pool_fold_updates(cec_recovery_pool *p, const cec_host_
         }
         so += pc.len;
     }
-    // waves: first fit over the tiles by R offset
+    // waves: greedy colouring of the tiles by R offset
     std::sort(tiles.begin(), tiles.end(), [](const Tile &x, const Tile &y) { return x.off < y.off; });
-    std::vector<uint64_t> wave_end;
-    std::vector<int> wave_of(tiles.size());
-    for (size_t t = 0; t < tiles.size(); ++t) {
-        size_t w = 0;
-        while (w < wave_end.size() && wave_end[w] > tiles[t].off) ++w;
-        if (w == wave_end.size()) wave_end.push_back(0);
-        wave_end[w] = tiles[t].off + tiles[t].len;
-        wave_of[t] = static_cast<int>(w);
-    }
-    const size_t nw = wave_end.size(), nt = tiles.size();
-    std::vector<size_t> wave_start(nw + 1, 0);
-    for (int w : wave_of) ++wave_start[w + 1];
-    for (size_t w = 0; w < nw; ++w) wave_start[w + 1] += wave_start[w];
-    // the tile buffers: the pool's own, or for a window wider than it, cached ones
-    const bool own = nt <= static_cast<size_t>(p->capacity);
-    Tile *h = own ? p->h_tiles : static_cast<Tile *>(map_cache().acquire(dev, nt * sizeof(Tile)));
-    Tile *d = own ? p->d_tiles : nullptr;
-    if (h && !d && hipHostGetDevicePointer(reinterpret_cast<void **>(&d), h, 0) != hipSuccess) d = nullptr;
-    if (!h || !d) {
-        (void)hipGetLastError();
-        if (h && !own) map_cache().release(dev, h, nt * sizeof(Tile));
+    const size_t nt = tiles.size();
+    std::vector<int> wave_of(nt);
+    const size_t nw = colour_intervals(
+        nt, [&](size_t t) { return std::pair<uint64_t, uint64_t>(tiles[t].off, tiles[t].off + tiles[t].len); },
+        [&](size_t t, int w) { wave_of[t] = w; });
+    std::vector<size_t> at(nw + 1, 0);  // counting sort by wave (stable)
+    for (int w : wave_of) ++at[w + 1];
+    for (size_t w = 0; w < nw; ++w) at[w + 1] += at[w];
+    std::vector<size_t> order(nt);
+    for (size_t t = 0; t < nt; ++t) order[at[wave_of[t]]++] = t;
+    // the tile buffer: the pool's own, or for a window wider than it, a cached one
+    Buf wide;
+    const Buf &tb = nt <= static_cast<size_t>(p->capacity) ? p->tiles : wide;
+    if (&tb == &wide && !wide.acquire_mapped(dev, nt * sizeof(Tile)))
         return fail(CEC_ENOMEM, "cec_recovery_pool_fold_updates: %zu tiles", nt);
-    }
-    {
-        std::vector<size_t> fill(wave_start.begin(), wave_start.end() - 1);
-        for (size_t t = 0; t < nt; ++t) h[fill[wave_of[t]]++] = tiles[t];
+    WaveTiles wt(tb.get<Tile>());
+    for (size_t t : order) {
+        wt.enter(wave_of[t]);
+        wt.add(tiles[t].off, tiles[t].src_off, tiles[t].len, tiles[t].pattern);  // (one tile each, as cut above)
     }
     // the packed diff pieces into R; pattern index = the update's data lid (recovery.c:123)
-    const Fold f = fold(p->code, p->lid_self, p->diff_dev, p->residual);
+    const Fold f = fold(p->code, p->lid_self, p->diff.alias(), p->residual.get());
     std::vector<char> used(p->code.k, 0);
     for (const Piece &pc : pieces) used[u[pc.upd].src_lid] = 1;
-    int rc = CEC_OK;
-    for (size_t w = 0; w < nw && !rc; ++w) {
-        const size_t lo = wave_start[w], n_wave = wave_start[w + 1] - lo;
-        rc = run_combos(dev, f.st, f.combos, TileSource::window(d + lo, h + lo, n_wave), s, &used);
-    }
-    if (!rc) rc = stream_wait(s, false);  // (the residual is in HBM; staging and tiles reusable)
-    if (rc) {  // an earlier wave may still read the diff staging and the tiles (the pool's own
-               // or borrowed), which the next call overwrites from the host
-        (void)hipStreamSynchronize(s);
-        (void)hipGetLastError();
-    }
-    if (!own) map_cache().release(dev, h, nt * sizeof(Tile));
-    return rc ? rc : total_units;
+    // an earlier wave may still read the diff staging and the tiles (the pool's own or `wide`,
+    // which goes back to the cache after the guard), which the next call overwrites from the host
+    InFlight guard(s);
+    for (int w = 0; w < wt.waves(); ++w)
+        if (int rc = run_combos(dev, f.st, f.combos, wt.window(w, tb.alias<Tile>()), s, &used)) return rc;
+    if (int rc = stream_wait(s, false)) return rc;  // (the residual is in HBM; staging and tiles reusable)
+    guard.dismiss();
+    return total_units;
 }
 
 // to_host: O[slot] = inv * R[slot] into out_host instead of out[lost][off].
@@ -673,7 +628,7 @@ static int pool_solve(cec_recovery_pool *p, const int *ids, int n, uint8_t *cons
     // index = x): one table per pool and engine in the coefficient cache, whatever the
     // mix of requests (`used` picks the kernel shape).
     Streams st;
-    const int s_residual = st.add(p->residual), s_out_host = to_host ? st.add(p->out_dev) : -1;
+    const int s_residual = st.add(p->residual.get()), s_out_host = to_host ? st.add(p->out.alias()) : -1;
     std::vector<Combo> combos(k);
     std::vector<char> used(k, 0);
     for (int x = 0; x < k; ++x) {
@@ -699,12 +654,12 @@ static int pool_solve(cec_recovery_pool *p, const int *ids, int n, uint8_t *cons
         used[lost] = 1;
         if (nt + r->nunits > static_cast<size_t>(p->capacity))  // (cannot happen once ids are distinct)
             return fail(CEC_EINVAL, "cec_recovery_pool_solve: more units than the tile buffer");
-        nt += append_tiles(p->h_tiles + nt, static_cast<uint64_t>(r->ub) * kTile,
+        nt += append_tiles(p->tiles.get<Tile>() + nt, static_cast<uint64_t>(r->ub) * kTile,
                            static_cast<uint64_t>(r->slot) * kTile, static_cast<uint32_t>(r->nunits) * kTile,
                            static_cast<uint32_t>(lost));
     }
     // (whole 4 KiB units on 4 KiB offsets, as the flush's)
-    if (int rc = run_combos(dev, st, combos, TileSource::whole_units(p->d_tiles, nt), s, &used)) return rc;
+    if (int rc = run_combos(dev, st, combos, TileSource::whole_units(p->tiles.alias<Tile>(), nt), s, &used)) return rc;
     if (int rc = stream_wait(s, to_host || any_host_memory(out, p->code.k))) return rc;
     for (int x = 0; x < n; ++x) {
         p->reqs[ids[x]].solved = true;
@@ -728,7 +683,7 @@ CEC_API int cec_recovery_pool_residual(cec_recovery_pool *p, int id, void *dst, 
     if (int rc = cec_recovery_pool_flush(p, stream); rc < 0) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     UseNote note_{p->uses, s};
-    HIP_TRY(hipMemcpyAsync(dst, p->residual + static_cast<size_t>(r->slot) * kTile,
+    HIP_TRY(hipMemcpyAsync(dst, p->residual.get() + static_cast<size_t>(r->slot) * kTile,
                            static_cast<size_t>(r->nunits) * kTile, hipMemcpyDefault, s));
     HIP_TRY(hipStreamSynchronize(s));
     return CEC_OK;

@@ -1,6 +1,7 @@
 // cec_recovery.inc -- online recovery over 4 KiB unit ranges (SURVEY §8f rank 2).
-// Included by cec_runtime.hip after cec_drain.inc (shares PackPool and the launch
-// internals); not a separate TU.
+// Included by cec_runtime.hip after cec_drain.inc (shares the launch internals); not a
+// separate TU.  HostStager takes PackPool / split_copy from cec_hostplan.hpp and Buf /
+// HalfPipe from cec_cache.inc, where device_view_of and any_host_memory (classify) live too.
 //
 // A cec_recovery is one recovery request on a participating parity
 // (recovery_queue_item, recovery.h:57-69).  The residual of the whole unit range lives
@@ -21,23 +22,11 @@ namespace {
 // copies chunk i into one half while the DMA of chunk i-1 (other half) runs.
 class HostStager {
   public:
-    ~HostStager() {
-        if (pinned_) {
-            for (int h = 0; h < 2; ++h)
-                if (pend_[h]) (void)hipEventSynchronize(ev_[h]);
-            pin_cache().release(dev_, pinned_, 2 * chunk_);
-        }
-        for (hipEvent_t e : ev_)
-            if (e) (void)hipEventDestroy(e);
-    }
+    ~HostStager() { (void)pipe_.wait_all(); }  // (then the pinned halves go back to the cache)
     int init(int dev, size_t chunk) {
         chunk_ = chunk;
-        dev_ = dev;
         // pinning pages costs milliseconds per 32 MiB: sessions share the pinned cache
-        pinned_ = static_cast<uint8_t *>(pin_cache().acquire(dev, 2 * chunk_));
-        if (!pinned_ ||
-            hipEventCreateWithFlags(&ev_[0], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&ev_[1], hipEventDisableTiming) != hipSuccess) {
+        if (!pinned_.acquire(pin_cache(), dev, 2 * chunk_) || pipe_.create(hipEventDisableTiming) != hipSuccess) {
             (void)hipGetLastError();
             return fail(CEC_ENOMEM, "pinned staging of 2 x %zu bytes", chunk_);
         }
@@ -45,26 +34,18 @@ class HostStager {
         return CEC_OK;
     }
     void pcopy(uint8_t *dst, const uint8_t *src, size_t len) {
-        const int T = pool_->size();
-        if (len < (size_t(1) << 20)) {
-            memcpy(dst, src, len);
-            return;
-        }
-        pool_->run([&](int t) {
-            const size_t lo = len * t / T, hi = len * (t + 1) / T;
-            memcpy(dst + lo, src + lo, hi - lo);
-        });
+        const CopyItem one{dst, src, len};
+        split_copy(pool_.get(), &one, 1, size_t(1) << 20);
     }
     // Host -> device; the copies are enqueued on s (complete in stream order).
     int upload(uint8_t *ddst, const uint8_t *hsrc, size_t len, hipStream_t s) {
         for (size_t o = 0; o < len; o += chunk_) {
             const size_t n = std::min(chunk_, len - o);
-            if (pend_[h_]) HIP_TRY(hipEventSynchronize(ev_[h_]));
-            uint8_t *pin = pinned_ + h_ * chunk_;
+            HIP_TRY(pipe_.wait(h_));
+            uint8_t *pin = pinned_.get() + h_ * chunk_;
             pcopy(pin, hsrc + o, n);
             HIP_TRY(hipMemcpyAsync(ddst + o, pin, n, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipEventRecord(ev_[h_], s));
-            pend_[h_] = true;
+            HIP_TRY(pipe_.record(h_, s));
             h_ ^= 1;
         }
         return CEC_OK;
@@ -75,14 +56,12 @@ class HostStager {
         int prev_h = -1;
         for (size_t o = 0; o < len; o += chunk_) {
             const size_t n = std::min(chunk_, len - o);
-            if (pend_[h_]) HIP_TRY(hipEventSynchronize(ev_[h_]));
-            HIP_TRY(hipMemcpyAsync(pinned_ + h_ * chunk_, dsrc + o, n, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipEventRecord(ev_[h_], s));
-            pend_[h_] = true;
+            HIP_TRY(pipe_.wait(h_));
+            HIP_TRY(hipMemcpyAsync(pinned_.get() + h_ * chunk_, dsrc + o, n, hipMemcpyDeviceToHost, s));
+            HIP_TRY(pipe_.record(h_, s));
             if (prev_h >= 0) {  // drain the previous chunk while this one is in flight
-                HIP_TRY(hipEventSynchronize(ev_[prev_h]));
-                pend_[prev_h] = false;
-                pcopy(hdst + prev_off, pinned_ + prev_h * chunk_, prev_n);
+                HIP_TRY(pipe_.wait(prev_h));
+                pcopy(hdst + prev_off, pinned_.get() + prev_h * chunk_, prev_n);
             }
             prev_h = h_;
             prev_off = o;
@@ -90,52 +69,19 @@ class HostStager {
             h_ ^= 1;
         }
         if (prev_h >= 0) {
-            HIP_TRY(hipEventSynchronize(ev_[prev_h]));
-            pend_[prev_h] = false;
-            pcopy(hdst + prev_off, pinned_ + prev_h * chunk_, prev_n);
+            HIP_TRY(pipe_.wait(prev_h));
+            pcopy(hdst + prev_off, pinned_.get() + prev_h * chunk_, prev_n);
         }
         return CEC_OK;
     }
 
   private:
     size_t chunk_ = 0;
-    int dev_ = 0;
-    uint8_t *pinned_ = nullptr;
-    hipEvent_t ev_[2] = {nullptr, nullptr};
-    bool pend_[2] = {false, false};
+    Buf pinned_;  // 2 x chunk_
+    HalfPipe pipe_;
     int h_ = 0;
     std::unique_ptr<PackPool> pool_;
 };
-
-// Device-usable view of p (device memory, or pinned / registered host memory mapped
-// into the device address space); NULL for pageable host memory.
-void *device_view_of(const void *p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    if (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged ||
-        at.type == hipMemoryTypeHost)
-        return at.devicePointer;
-    return nullptr;
-}
-
-// Any of the n outputs in host memory (pinned / registered): the synchronous call that
-// wrote them then waits with host_results (stream_wait).
-bool any_host_memory(uint8_t *const *out, int n) {
-    for (int i = 0; out && i < n; ++i) {
-        if (!out[i]) continue;
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, out[i]) != hipSuccess) {
-            (void)hipGetLastError();
-            return true;  // unknown: be safe
-        }
-        // pinned / registered host memory, or managed memory the host may read on return
-        if (at.type == hipMemoryTypeHost || at.type == hipMemoryTypeManaged) return true;
-    }
-    return false;
-}
 
 }  // namespace
 

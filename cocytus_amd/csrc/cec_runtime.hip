@@ -28,6 +28,7 @@
 #include "../../include/galois.h"
 #include "../../include/jerasure.h"
 #include "../../include/reed_sol.h"
+#include "cec_hostplan.hpp"
 #include "cec_kernels.hpp"
 #include "gf256.hpp"
 
@@ -432,6 +433,31 @@ struct TileSource {
     }
     // ... whose tiles the caller knows to be whole 4 KiB units at 4 KiB offsets.
     static TileSource whole_units(const Tile *d, size_t n) { return {d, n, n, 0, nullptr}; }
+};
+
+// The tile list of an op whose items run in overlap waves, one launch per wave: items
+// are added in wave order into the caller's host tile buffer (which must hold them),
+// and each wave's range is kept for its launch window.
+struct WaveTiles {
+    Tile *h;
+    size_t n = 0;               // tiles so far
+    std::vector<size_t> first;  // first tile of each wave begun
+    int cur = -1;
+    explicit WaveTiles(Tile *host) : h(host) {}
+    void begin_wave() { first.push_back(n); }
+    void enter(int wave) {  // begin_wave() whenever the items' wave changes
+        if (wave != cur) begin_wave();
+        cur = wave;
+    }
+    void add(uint64_t off, uint64_t src_off, uint32_t len, uint32_t pattern) {
+        n += append_tiles(h + n, off, src_off, len, pattern);
+    }
+    int waves() const { return static_cast<int>(first.size()); }
+    // Wave w's launch, d being the device address of h; n_tiles == 0: nothing to launch.
+    TileSource window(int w, const Tile *d) const {
+        const size_t lo = first[w], hi = w + 1 < waves() ? first[w + 1] : n;
+        return TileSource::window(d + lo, h + lo, hi - lo);
+    }
 };
 
 // Workgroups per tile (log2).  Full tiles on 128-B lines stream fastest as four
@@ -1235,11 +1261,10 @@ __global__ void cec_signal_kernel(uint32_t *flag, uint32_t v) {
 namespace {
 struct SignalCtx {  // per thread and device: a mapped pinned completion word
     int device = -1;
-    uint32_t *flag = nullptr, *flag_dev = nullptr;
+    Buf flag;  // (idle when released: every wait completed before its call returned)
     uint32_t seq = 0;
     hipEvent_t fence = nullptr;  // recorded before the signal: a system-scope release
-    ~SignalCtx() {  // (idle: every wait completed before its call returned)
-        map_cache().release(device, flag, 64);
+    ~SignalCtx() {
         if (fence) (void)hipEventDestroy(fence);
     }
 };
@@ -1263,12 +1288,9 @@ static int stream_wait(hipStream_t s, bool host_results, bool waves_released = f
     HIP_TRY(hipGetDevice(&dev));
     SignalCtx &c = t_signal;
     if (c.device != dev) {
-        map_cache().release(c.device, c.flag, 64);
-        c.flag = c.flag_dev = nullptr;
-        c.flag = static_cast<uint32_t *>(map_cache().acquire(dev, 64));
-        if (!c.flag) return fail(CEC_ENOMEM, "completion flag");
-        HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&c.flag_dev), c.flag, 0));
-        __atomic_store_n(c.flag, 0u, __ATOMIC_RELEASE);
+        c.device = -1;
+        if (!c.flag.acquire_mapped(dev, 64)) return fail(CEC_ENOMEM, "completion flag");
+        __atomic_store_n(c.flag.get<uint32_t>(), 0u, __ATOMIC_RELEASE);
         c.seq = 0;
         if (c.fence) (void)hipEventDestroy(c.fence);
         c.fence = nullptr;
@@ -1291,11 +1313,12 @@ static int stream_wait(hipStream_t s, bool host_results, bool waves_released = f
     // hipEventQuery of that event instead of the signal kernel's flag measured the same
     // per call: archive/profiles/r02_evidence_s3/wait_mode_ab.jsonl.)
     if (fence) HIP_TRY(hipEventRecord(c.fence, s));
-    hipLaunchKernelGGL(cec_signal_kernel, dim3(1), dim3(1), 0, s, c.flag_dev, v);
+    hipLaunchKernelGGL(cec_signal_kernel, dim3(1), dim3(1), 0, s, c.flag.alias<uint32_t>(), v);
     HIP_TRY(hipGetLastError());
     const auto t0 = std::chrono::steady_clock::now();
+    const uint32_t *flag = c.flag.get<uint32_t>();
     for (uint32_t i = 1;; ++i) {
-        if (__atomic_load_n(c.flag, __ATOMIC_ACQUIRE) == v) return CEC_OK;
+        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == v) return CEC_OK;
         __builtin_ia32_pause();
         if ((i & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(200))
             break;
@@ -1491,10 +1514,8 @@ namespace {
 struct DropInCtx {
     int device = -1;
     hipStream_t stream = nullptr;
-    uint8_t *dsrc = nullptr, *ddst = nullptr;
-    size_t cap = 0;
-    uint8_t *zc = nullptr;  // mapped pinned buffer (2 x zc_cap) for zero-copy calls
-    void *zc_dev = nullptr;  // its device address
+    Buf dsrc, ddst;  // device staging of the chunked path
+    Buf zc;  // mapped pinned buffer (2 x zc_cap) for zero-copy calls
     size_t zc_cap = 0;
     ~DropInCtx() {
         if (stream) {
@@ -1506,12 +1527,10 @@ struct DropInCtx {
     // Buffers back to the process caches (idle: every call completed before returning);
     // freeing them would wait for the whole device.
     void release() {
-        dev_cache().release(device, dsrc, cap);
-        dev_cache().release(device, ddst, cap);
-        map_cache().release(device, zc, 2 * zc_cap);
-        dsrc = ddst = zc = nullptr;
-        zc_dev = nullptr;
-        cap = zc_cap = 0;
+        dsrc.release();
+        ddst.release();
+        zc.release();
+        zc_cap = 0;
     }
 };
 thread_local DropInCtx t_ctx;
@@ -1528,22 +1547,6 @@ size_t zero_copy_max() {
     return v;
 }
 
-// Device-usable address for p, or NULL if p is pageable host memory; *host: the host
-// may read p on return without a copy -- pinned host memory (the kernel reaches it over
-// PCIe) or managed memory -- so a result written there needs the system-scope release.
-void *device_view(void *p, bool *host) {
-    *host = false;
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    *host = at.type == hipMemoryTypeHost || at.type == hipMemoryTypeManaged;
-    if (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged ||
-        at.type == hipMemoryTypeHost)
-        return at.devicePointer;
-    return nullptr;
-}
 }  // namespace
 
 #define DROPIN_CHECK(expr)                                                                  \
@@ -1584,8 +1587,9 @@ CEC_API void galois_w08_region_multiply(char *region, int multby, int nbytes, ch
     const size_t n = static_cast<size_t>(nbytes);
     char *dst = r2 ? r2 : region;
     const int mode_add = r2 ? add : 0;
-    bool hs = false, hd = false;
-    void *vs = device_view(region, &hs), *vd = device_view(dst, &hd);
+    const PtrKind ks = classify(region), kd = classify(dst);
+    void *const vs = ks.dev, *const vd = kd.dev;
+    const bool hs = ks.host, hd = kd.host;
     if (vs && vd) {  // device-resident (or pinned/mapped): run in place
         bool rel = false;  // (a host-visible destination: the kernel's waves release it themselves)
         DROPIN_CHECK(region_launch(dev, vs, multby, n, vd, mode_add, c.stream, true, hd ? kFlagSysRelease : 0, &rel));
@@ -1596,16 +1600,13 @@ CEC_API void galois_w08_region_multiply(char *region, int multby, int nbytes, ch
     const bool host_ok = (!vs || hs) && (!vd || hd);  // both reachable by the CPU's memcpy
     if (host_ok && n <= zero_copy_max()) {  // small host call: zero-copy through mapped pinned memory
         if (c.zc_cap < n16) {
-            map_cache().release(dev, c.zc, 2 * c.zc_cap);
             c.zc_cap = std::max(n16, size_t(64) << 10);
-            c.zc = static_cast<uint8_t *>(map_cache().acquire(dev, 2 * c.zc_cap));
-            if (!c.zc) die("galois_w08_region_multiply: mapped staging allocation failed");
-            DROPIN_HIP(hipHostGetDevicePointer(&c.zc_dev, c.zc, 0));
+            if (!c.zc.acquire_mapped(dev, 2 * c.zc_cap)) die("galois_w08_region_multiply: mapped staging allocation failed");
         }
-        uint8_t *zs = c.zc, *zd = c.zc + c.zc_cap;
+        uint8_t *zs = c.zc.get(), *zd = zs + c.zc_cap;
         memcpy(zs, region, n);
         if (mode_add) memcpy(zd, dst, n);
-        uint8_t *ds = static_cast<uint8_t *>(c.zc_dev), *dd = ds + c.zc_cap;
+        uint8_t *ds = c.zc.alias(), *dd = ds + c.zc_cap;
         // n16 bytes: whole 16-byte chunks only, no byte scatter over PCIe (the padding's
         // results are not copied back)
         bool rel = false;
@@ -1617,21 +1618,17 @@ CEC_API void galois_w08_region_multiply(char *region, int multby, int nbytes, ch
     // larger host buffers (or a device operand with a host result): stage through
     // device memory chunk by chunk
     const size_t want = std::min(n, kStageChunk);
-    if (c.cap < want) {
-        dev_cache().release(dev, c.dsrc, c.cap);
-        dev_cache().release(dev, c.ddst, c.cap);
-        c.dsrc = static_cast<uint8_t *>(dev_cache().acquire(dev, want));
-        c.ddst = static_cast<uint8_t *>(dev_cache().acquire(dev, want));
-        if (!c.dsrc || !c.ddst) die("galois_w08_region_multiply: device staging allocation failed");
-        c.cap = want;
-    }
+    if (c.ddst.bytes() < want &&
+        (!c.dsrc.acquire(dev_cache(), dev, want) || !c.ddst.acquire(dev_cache(), dev, want)))
+        die("galois_w08_region_multiply: device staging allocation failed");
+    uint8_t *const dsrc = c.dsrc.get(), *const ddst = c.ddst.get();
     for (size_t o = 0; o < n; o += kStageChunk) {
         const size_t len = std::min(kStageChunk, n - o);
-        DROPIN_HIP(hipMemcpyAsync(c.dsrc, region + o, len, hipMemcpyDefault, c.stream));
+        DROPIN_HIP(hipMemcpyAsync(dsrc, region + o, len, hipMemcpyDefault, c.stream));
         if (mode_add)
-            DROPIN_HIP(hipMemcpyAsync(c.ddst, dst + o, len, hipMemcpyDefault, c.stream));
-        DROPIN_CHECK(region_launch(dev, c.dsrc, multby, len, c.ddst, mode_add, c.stream, true));
-        DROPIN_HIP(hipMemcpyAsync(dst + o, c.ddst, len, hipMemcpyDefault, c.stream));
+            DROPIN_HIP(hipMemcpyAsync(ddst, dst + o, len, hipMemcpyDefault, c.stream));
+        DROPIN_CHECK(region_launch(dev, dsrc, multby, len, ddst, mode_add, c.stream, true));
+        DROPIN_HIP(hipMemcpyAsync(dst + o, ddst, len, hipMemcpyDefault, c.stream));
         DROPIN_HIP(hipStreamSynchronize(c.stream));
     }
     // (the result came back by DMA, complete and visible when the stream synchronised)

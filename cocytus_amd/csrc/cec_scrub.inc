@@ -48,6 +48,7 @@ static_assert(CEC_KERNEL_SCRUB == 3, "cec_launch_record::kind");
 struct cec_scrub_report {
     int device = -1;
     uint64_t max_tiles = 0;
+    Buf d_mem, h_mem;           // device words and their pinned mirror (cec_cache.inc), viewed as:
     uint32_t *d_buf = nullptr;  // kScrubHead + max_tiles words: counter, then one word per tile
     uint32_t *h_buf = nullptr;  // pinned mirror, same layout
     Tracker uses;
@@ -77,14 +78,12 @@ CEC_API int cec_scrub_create(cec_scrub_report **out, uint64_t max_tiles) {
     s->device = dev;
     s->max_tiles = max_tiles;
     const size_t bytes = sizeof(uint32_t) * (kScrubHead + max_tiles);
-    s->d_buf = static_cast<uint32_t *>(dev_cache().acquire(dev, bytes));
-    s->h_buf = static_cast<uint32_t *>(pin_cache().acquire(dev, bytes));
-    if (!s->d_buf || !s->h_buf) {
-        dev_cache().release(dev, s->d_buf, bytes);
-        pin_cache().release(dev, s->h_buf, bytes);
+    if (!s->d_mem.acquire(dev_cache(), dev, bytes) || !s->h_mem.acquire(pin_cache(), dev, bytes)) {
         delete s;
         return fail(CEC_ENOMEM, "cec_scrub_create: %zu bytes of report", bytes);
     }
+    s->d_buf = s->d_mem.get<uint32_t>();
+    s->h_buf = s->h_mem.get<uint32_t>();
     *out = s;
     return CEC_OK;
 }
@@ -92,10 +91,7 @@ CEC_API int cec_scrub_create(cec_scrub_report **out, uint64_t max_tiles) {
 CEC_API int cec_scrub_destroy(cec_scrub_report *s) {
     if (!s) return CEC_OK;
     (void)s->uses.wait(s->device);  // its own runs, not the device
-    const size_t bytes = sizeof(uint32_t) * (kScrubHead + s->max_tiles);
-    dev_cache().release(s->device, s->d_buf, bytes);
-    pin_cache().release(s->device, s->h_buf, bytes);
-    delete s;
+    delete s;  // (its buffers go back to the caches)
     return CEC_OK;
 }
 

@@ -1,7 +1,7 @@
-// tests/drain_c/hb_waves_main.cpp -- the host batch's wave planning (cec_hostbatch.inc:
-// the pieces, the range-assign / range-max tree and hb_cluster_waves), spliced from the
-// shipped source (at the marker in the namespace below) by tests/test_abi.py and run under ASan + UBSan on random
-// clusters.  The properties cec_region_multiply_batch relies on:
+// tests/drain_c/hb_waves_main.cpp -- the host batch's wave planning (the pieces, the
+// range-assign / range-max tree and hb_cluster_waves of the shipped
+// cocytus_amd/csrc/cec_hostplan.hpp), compiled by tests/test_abi.py and run under
+// ASan + UBSan on random clusters.  The properties cec_region_multiply_batch relies on:
 //   * two overlapping pieces never share a wave;
 //   * in a cluster holding a write (add = 0 or a base), a piece of a later job runs in a
 //     later wave than every earlier-job piece it overlaps (the sequential chain's order);
@@ -15,9 +15,9 @@
 #include <random>
 #include <vector>
 
-namespace {
-// HB_FUNCS
-}  // namespace
+#include "cec_hostplan.hpp"
+
+using namespace cec;
 
 int main() {
     std::mt19937_64 rng(12345);

@@ -1,23 +1,40 @@
 // tests/drain_c/waves_main.cpp -- property check of the drainer's wave colouring on the
-// CPU: tests/test_abi.py::test_drain_wave_colouring splices the shipped functions
-// (sort_by_addr .. overlap_waves of cocytus_amd/csrc/cec_drain.inc) in at WAVES_FUNCS and
-// compiles this under ASan + UBSan.  No two overlapping updates may share a wave; a batch
-// of distinct values is one wave; the address sort is ordered.
+// CPU: tests/test_abi.py::test_drain_wave_colouring compiles this against the shipped
+// cocytus_amd/csrc/cec_hostplan.hpp (radix_sort, colour_intervals, overlap_waves) under
+// ASan + UBSan.  No two overlapping updates may share a wave; a batch of distinct values is
+// one wave; without empty updates the wave count is the deepest overlap; the address sort
+// is ordered.  The same colouring over unit-aligned tile intervals, as the recovery pool's
+// fold_updates feeds it, has the same two properties.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <random>
 #include <vector>
-typedef struct { const void *buf; uint64_t addr; uint32_t len; uint32_t src_lid; } cec_host_update;
-// WAVES_FUNCS
+
+#include "cec_hostplan.hpp"
+
+using namespace cec;
+
+// The deepest overlap of the non-empty intervals [lo[i], hi[i]): reached at some start.
+static int depth_of(const std::vector<uint64_t> &lo, const std::vector<uint64_t> &hi) {
+    int depth = 0;
+    for (size_t i = 0; i < lo.size(); ++i) {
+        if (hi[i] <= lo[i]) continue;
+        int d = 0;
+        for (size_t j = 0; j < lo.size(); ++j) d += lo[j] <= lo[i] && lo[i] < hi[j];
+        depth = std::max(depth, d);
+    }
+    return depth;
+}
 
 int main() {
     std::mt19937_64 r(5);
-    for (int t = 0; t < 3000; ++t) {
+    for (int t = 0; t < 4000; ++t) {  // (the last 1,000 batches: no empty update)
         int n = 1 + r() % 200;
         std::vector<cec_host_update> u(n);
         const uint64_t span = 1 + r() % (1ull << (r() % 34));
         for (auto &x : u) { x.addr = r() % span; x.len = r() % 4 ? (uint32_t)(r() % 5000) : 0; x.src_lid = 0; x.buf = nullptr; }
+        if (t >= 3000) for (auto &x : u) if (!x.len) x.len = 1 + (uint32_t)(r() % 5000);
         if (t % 3 == 0) for (int i = 0; i < n; ++i) { u[i].addr = (uint64_t)i * 4098 + (t % 7) * (1ull << 33); u[i].len = 4098; }
         std::vector<int> w;
         int nw = overlap_waves(u.data(), n, w);
@@ -30,12 +47,49 @@ int main() {
             if (ov) { printf("overlap in wave t=%d\n", t); return 1; }
         }
         if (t % 3 == 0 && nw != 1) { printf("fast path missed\n"); return 1; }
+        bool any_empty = false;
+        std::vector<uint64_t> lo(n), hi(n);
+        for (int i = 0; i < n; ++i) { lo[i] = u[i].addr; hi[i] = u[i].addr + u[i].len; any_empty |= !u[i].len; }
+        if (!any_empty && nw != depth_of(lo, hi)) { printf("waves %d != depth %d t=%d\n", nw, depth_of(lo, hi), t); return 1; }
+    }
+    // the pool's feed: the 4 KiB-cut tiles of pieces inside slots of 1-4 units, sorted by offset
+    for (int t = 0; t < 2000; ++t) {
+        const int slots = 1 + r() % 8, pieces = 1 + r() % 64;
+        std::vector<uint64_t> slot_off(slots), slot_len(slots), lo, hi;
+        uint64_t at = 0;
+        for (int s = 0; s < slots; ++s) { slot_off[s] = at; slot_len[s] = (1 + r() % 4) * 4096; at += slot_len[s]; }
+        std::vector<std::pair<uint64_t, uint64_t>> tiles;
+        for (int p = 0; p < pieces; ++p) {
+            const int s = r() % slots;
+            const uint64_t a = r() % slot_len[s], b = a + 1 + r() % (slot_len[s] - a);
+            for (uint64_t o = slot_off[s] + a, e = slot_off[s] + b; o < e;) {  // append_tiles' cut
+                const uint64_t step = std::min<uint64_t>(4096 - o % 4096, e - o);
+                tiles.emplace_back(o, o + step);
+                o += step;
+            }
+        }
+        std::sort(tiles.begin(), tiles.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
+        std::vector<int> w(tiles.size(), -1);
+        const int nw = colour_intervals(tiles.size(), [&](size_t i) { return tiles[i]; }, [&](size_t i, int x) { w[i] = x; });
+        for (size_t i = 0; i < tiles.size(); ++i) {
+            if (w[i] < 0 || w[i] >= nw) { printf("tile wave out of range t=%d\n", t); return 1; }
+            for (size_t j = i + 1; j < tiles.size(); ++j)
+                if (w[i] == w[j] && tiles[i].first < tiles[j].second && tiles[j].first < tiles[i].second) {
+                    printf("tiles overlap in wave t=%d\n", t);
+                    return 1;
+                }
+            lo.push_back(tiles[i].first);
+            hi.push_back(tiles[i].second);
+        }
+        if (nw != depth_of(lo, hi)) { printf("tile waves %d != depth %d t=%d\n", nw, depth_of(lo, hi), t); return 1; }
     }
     std::vector<cec_host_update> u(70000);
     std::mt19937 g(1); std::vector<int> p(u.size()); for (size_t i=0;i<p.size();++i) p[i]=i; std::shuffle(p.begin(),p.end(),g);
     for (size_t i=0;i<u.size();++i) u[i] = {nullptr, (uint64_t)p[i]*4098, 4098, 0};
-    std::vector<cec_host_update> byaddr_check(u);
-    std::vector<std::pair<uint64_t,int>> s; sort_by_addr(u.data(), (int)u.size(), s);
+    std::vector<std::pair<uint64_t,int>> s(u.size());
+    for (size_t i=0;i<u.size();++i) s[i] = {u[i].addr, (int)i};
+    radix_sort(s);
     for (size_t i=1;i<s.size();++i) if (s[i-1].first > s[i].first) { printf("not sorted\n"); return 1; }
+    for (size_t i=0;i<s.size();++i) if (u[s[i].second].addr != s[i].first) { printf("index lost\n"); return 1; }
     printf("ok\n");
 }
