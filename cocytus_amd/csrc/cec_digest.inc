@@ -7,6 +7,10 @@
 // arena (cec_digest, 32 B per 4 KiB unit), ships the digests, and the leader runs the
 // scrub's syndrome and ratio test on them (cec_scrub_digests) into the same
 // cec_scrub_report -- wait / findings / classify / repair are cec_scrub.inc's, unchanged.
+// Live digests: a process keeps its digest array current instead of taking it anew --
+// cec_digest_apply_diffs folds every applied diff into it (digest_update_launch, which the
+// drainer of cec_drain.inc calls once per round), and cec_digest_verify_region compares it
+// with a fresh one through the same check.
 // Built from the library's parts: a TileSource to walk, launch_countdown, scrub_patterns +
 // pattern_tables for the check's coefficients, the capacity ladder, record_launch.
 
@@ -43,7 +47,8 @@ Capacity launch_digest_check(int k, int lt, const DigestCheckArgs &a, uint32_t g
 }  // namespace
 
 static_assert(CEC_DIGEST_BYTES == kDigestBytes, "digest size");
-static_assert(CEC_KERNEL_DIGEST == 4 && CEC_KERNEL_DIGEST_CHECK == 5, "cec_launch_record::kind");
+static_assert(CEC_KERNEL_DIGEST == 4 && CEC_KERNEL_DIGEST_CHECK == 5 && CEC_KERNEL_DIGEST_UPDATE == 6,
+              "cec_launch_record::kind");
 static_assert(CEC_MAX_K + CEC_MAX_M == kDigestArenas && kDigestArenas == kScrubStreams, "a whole group per launch");
 
 static int digest_common(const char *op, int n, const uint8_t *const *arenas, uint8_t *const *digests,
@@ -101,6 +106,68 @@ CEC_API int cec_digest_region(int n, const uint8_t *const *arenas, uint8_t *cons
     return digest_common("cec_digest_region", n, arenas, digests, nullptr, len, stream);
 }
 
+// The end of a live digest array of n_units units, as an arena offset.
+static int digest_limit(const char *op, uint64_t n_units, uint64_t *limit) {
+    if (n_units > (UINT64_MAX >> 12)) return fail(CEC_EINVAL, "%s: n_units %llu is no unit count", op,
+                                                  static_cast<unsigned long long>(n_units));
+    *limit = n_units * kTile;
+    return CEC_OK;
+}
+
+// One digest_update_kernel launch: every tile of `src` (arena offset, src_off into `diffs`,
+// pattern = source data lid) folded into the live digests of lid_self, which the caller has
+// checked to hold every tile's unit.  One wave per tile, four per workgroup.
+static int digest_update_launch(int dev, const Code &code, int lid_self, const uint8_t *diffs, uint8_t *digests,
+                                const TileSource &src, hipStream_t stream) {
+    if (src.n_tiles > kDigestMaxWork)
+        return fail(CEC_EINVAL, "digest update: %llu tiles, one launch holds %llu",
+                    static_cast<unsigned long long>(src.n_tiles), static_cast<unsigned long long>(kDigestMaxWork));
+    if (int rc = launch_countdown()) return rc;
+    std::vector<Pattern> pats(1, blank_pattern());
+    pats[0].n_in = code.k;
+    pats[0].n_out = 1;
+    for (int j = 0; j < code.k; ++j) set_coef(pats[0], 0, j, code.at(lid_self, j), CEC_ENGINE_PERM);
+    PatEntry *entry = nullptr;
+    if (int rc = pattern_tables(dev, pats, {}, stream, &entry)) return rc;
+    DigestUpdateArgs a;
+    memset(&a, 0, sizeof a);
+    a.diffs = diffs;
+    a.digests = digests;
+    a.tiles = src.tiles;
+    a.pattern = reinterpret_cast<const Pattern *>(entry->d);
+    a.n_tiles = static_cast<uint32_t>(src.n_tiles);
+    const uint32_t grid = static_cast<uint32_t>((src.n_tiles + 3) / 4);
+    hipLaunchKernelGGL(digest_update_kernel, dim3(grid), dim3(kBlock), 0, stream, a);
+    if (src.uses) src.uses->note(stream);
+    pattern_done(entry);
+    HIP_TRY(hipGetLastError());
+    record_launch(CEC_KERNEL_DIGEST_UPDATE, {1, 0}, kAccAll, false, 0, 0, grid, src.n_tiles, 0);
+    return CEC_OK;
+}
+
+CEC_API int cec_digest_apply_diffs(int k, int m, const int *matrix, int lid_self, const uint8_t *diffs,
+                                   uint8_t *digests, uint64_t n_units, const cec_plan *plan, void *stream) {
+    const char *op = "cec_digest_apply_diffs";
+    if (int r = check_code(k, m, matrix)) return r;
+    if (lid_self < 0 || lid_self >= k + m) return fail(CEC_EINVAL, "%s: lid_self %d outside [0, %d)", op, lid_self, k + m);
+    if (!diffs || !digests || !plan) return fail(CEC_EINVAL, "%s: NULL diffs, digests or plan", op);
+    if (reinterpret_cast<uintptr_t>(digests) & 15) return fail(CEC_EINVAL, "%s: digests is not 16-byte aligned", op);
+    if (plan->n_ext && plan->max_pattern >= static_cast<uint32_t>(k))
+        return fail(CEC_EINVAL, "%s: an extent names source shard %u (k = %d)", op, plan->max_pattern, k);
+    uint64_t limit;
+    if (int r = digest_limit(op, n_units, &limit)) return r;
+    if (plan->max_end_ext >= 0 && plan->max_end > limit)
+        return fail(CEC_EINVAL, "%s: extent %d ends at %llu, beyond n_units * 4096 = %llu", op, plan->max_end_ext,
+                    static_cast<unsigned long long>(plan->max_end), static_cast<unsigned long long>(limit));
+    int dev;
+    if (int r = current_device(&dev)) return r;
+    TileSource src;
+    if (int r = TileSource::of_plan(plan, dev, &src)) return r;
+    t_last_engine = CEC_ENGINE_PERM;  // whatever cec_set_engine says
+    if (src.n_tiles == 0) return CEC_OK;
+    return digest_update_launch(dev, Code{k, m, matrix}, lid_self, diffs, digests, src, static_cast<hipStream_t>(stream));
+}
+
 // One launch: the digests of parities [p0, p0 + lt) against the k data digests, one lane
 // per unit.  Reads no arena and no tile: the source only counts the units.
 static int digest_check_launch(int dev, cec_scrub_report *s, int k, int m, const int *matrix,
@@ -141,4 +208,13 @@ CEC_API int cec_scrub_digests_region(cec_scrub_report *s, int k, int m, const in
                                      size_t len, void *stream) {
     return scrub_common("cec_scrub_digests_region", true, s, k, m, matrix, data_digests, parity_digests, nullptr, len,
                         stream);
+}
+
+// A process's check of itself: the digest check of the code k = 1, m = 1, matrix {1, 1}, with
+// `fresh` as the data digests and `live` as the parity's -- the syndrome is live ^ fresh.
+CEC_API int cec_digest_verify_region(cec_scrub_report *s, const uint8_t *live, const uint8_t *fresh, size_t len,
+                                     void *stream) {
+    static const int kSelf[2] = {1, 1};
+    if (!live || !fresh) return fail(CEC_EINVAL, "cec_digest_verify_region: NULL digest array");
+    return scrub_common("cec_digest_verify_region", true, s, 1, 1, kSelf, &fresh, &live, nullptr, len, stream);
 }

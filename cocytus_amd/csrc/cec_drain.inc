@@ -14,7 +14,10 @@
 //   * the ordered list is cut into rounds of <= kRoundBytes; a pool of host threads
 //     packs round r into one half of a double-buffered pinned staging area while the
 //     H2D copy and the fold kernel of round r-1 (other half) run on the stream;
-//   * the fold is cec_apply_diffs' kernel (pattern j: parity ^= MATRIX(self, j) * diff).
+//   * the fold is cec_apply_diffs' kernel (pattern j: parity ^= MATRIX(self, j) * diff);
+//   * with live digests attached (cec_drainer_set_digests) each round ends with one
+//     digest_update_kernel launch (cec_digest.inc) over the round's whole tile list, behind
+//     its fold launches and reading the same staging: its atomics need no overlap waves.
 #include <memory>
 
 constexpr size_t kRoundBytes = size_t(16) << 20;  // pipelining granularity
@@ -36,7 +39,15 @@ struct cec_drainer {
     // caller's thread into mapped pinned staging that the kernel reads in place, tile list
     // likewise, the low-latency completion -- no pack threads, no uploads (on first use)
     Buf sm, smt;
+    // the parity's live digests (cec_drainer_set_digests; NULL: none), kept current by every apply
+    uint8_t *digests = nullptr;
+    uint64_t digest_limit = 0;  // n_units * 4096: no update may end beyond it
 };
+
+// cec_digest.inc
+static int digest_limit(const char *op, uint64_t n_units, uint64_t *limit);
+static int digest_update_launch(int dev, const Code &code, int lid_self, const uint8_t *diffs, uint8_t *digests,
+                                const TileSource &src, hipStream_t stream);
 
 constexpr size_t kDrainSmallBytes = size_t(1) << 20;
 constexpr size_t kDrainSmallTiles = 8192;
@@ -88,6 +99,19 @@ CEC_API int cec_drainer_create(cec_drainer **out, int k, int m, const int *matri
 
 CEC_API int cec_drainer_last_launches(const cec_drainer *d) { return d ? d->last_launches : 0; }
 
+CEC_API int cec_drainer_set_digests(cec_drainer *d, uint8_t *digests, uint64_t n_units) {
+    if (!d) return fail(CEC_EINVAL, "cec_drainer_set_digests: drainer is NULL");
+    uint64_t limit = 0;
+    if (digests) {
+        if (reinterpret_cast<uintptr_t>(digests) & 15)
+            return fail(CEC_EINVAL, "cec_drainer_set_digests: digests is not 16-byte aligned");
+        if (int r = digest_limit("cec_drainer_set_digests", n_units, &limit)) return r;
+    }
+    d->digests = digests;
+    d->digest_limit = limit;
+    return CEC_OK;
+}
+
 CEC_API uint8_t *cec_drainer_staging(cec_drainer *d, size_t *capacity) {
     if (!d) return nullptr;
     if (capacity) *capacity = 2 * d->half;
@@ -102,6 +126,10 @@ static int drainer_check(const cec_drainer *d, const cec_host_update *u, int n, 
             return fail(CEC_EINVAL, "%s: update %d: src_lid %u / buf", op, i, u[i].src_lid);
         if (u[i].len > d->half)
             return fail(CEC_EINVAL, "%s: update %d (%u B) exceeds staging", op, i, u[i].len);
+        if (d->digests && u[i].len && (u[i].addr > d->digest_limit || u[i].len > d->digest_limit - u[i].addr))
+            return fail(CEC_EINVAL, "%s: update %d ends at %llu, beyond the attached digests' n_units * 4096 = %llu",
+                        op, i, static_cast<unsigned long long>(u[i].addr + u[i].len),
+                        static_cast<unsigned long long>(d->digest_limit));
     }
     return CEC_OK;
 }
@@ -111,7 +139,8 @@ CEC_API int cec_drainer_validate(const cec_drainer *d, const cec_host_update *u,
 }
 
 // The fold launches of one round, one per overlap wave of `wt` (its tiles at dt on the
-// device).  `stage`: the device address the tiles' src_off count from.
+// device), then the round's digest update where digests are attached.  `stage`: the device
+// address the tiles' src_off count from.
 static int drainer_fold(cec_drainer *d, int dev, const uint8_t *stage, uint8_t *parity, const Tile *dt,
                         const WaveTiles &wt, hipStream_t s) {
     const Fold f = fold(d->code, d->lid_self, stage, parity);  // pattern j = source shard j
@@ -119,6 +148,10 @@ static int drainer_fold(cec_drainer *d, int dev, const uint8_t *stage, uint8_t *
         const TileSource wave = wt.window(w, dt);
         if (!wave.n_tiles) continue;
         if (int r = run_combos(dev, f.st, f.combos, wave, s)) return r;
+        ++d->last_launches;
+    }
+    if (d->digests && wt.n) {
+        if (int r = digest_update_launch(dev, d->code, d->lid_self, stage, d->digests, wt.all(dt), s)) return r;
         ++d->last_launches;
     }
     return CEC_OK;

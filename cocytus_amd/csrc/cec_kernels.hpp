@@ -676,6 +676,28 @@ __device__ inline uint32_t wave_xor_to_last(uint32_t x) {
     x = dpp_xor<0x143, 0xC>(x);  // row_bcast31: row 3 ^= row 1
     return x;
 }
+// The digest of the unit whose chunks lane, lane + 64, lane + 128, lane + 192 this lane holds
+// in c[0..3]: the lane's shares of D0 and D1, then the wave's XOR; lane 63 ends with d[0..8).
+__device__ inline void digest_wave_total(const uint4 (&c)[4], uint32_t lane, uint32_t (&d)[8]) {
+    uint32_t tab[5];
+#pragma unroll
+    for (int w = 0; w < 5; ++w) tab[w] = kDigestLaneTabs.w[w][lane];
+    constexpr PermTab k40 = make_perm_tab(0x40);
+    const uint32_t t40[5] = {k40.w[0], k40.w[1], k40.w[2], k40.w[3], k40.w[4]};
+
+    const uint32_t cw[4][4] = {{c[0].x, c[0].y, c[0].z, c[0].w}, {c[1].x, c[1].y, c[1].z, c[1].w},
+                               {c[2].x, c[2].y, c[2].z, c[2].w}, {c[3].x, c[3].y, c[3].z, c[3].w}};
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const uint32_t hi6 = cw[1][w] ^ cw[3][w];  // chunks whose index has bit 6
+        const uint32_t hi7 = cw[2][w] ^ cw[3][w];  // ... bit 7
+        const uint32_t A = cw[0][w] ^ cw[2][w] ^ hi6;
+        d[w] = A;
+        d[4 + w] = perm_mul(A, tab) ^ perm_mul(hi6 ^ xtime4(hi7), t40);
+    }
+#pragma unroll
+    for (int w = 0; w < 8; ++w) d[w] = wave_xor_to_last(d[w]);
+}
 
 __global__ __launch_bounds__(kBlock) void digest_kernel(DigestArgs a) {
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -725,6 +747,90 @@ __global__ __launch_bounds__(kBlock) void digest_kernel(DigestArgs a) {
         v1.x = d[4]; v1.y = d[5]; v1.z = d[6]; v1.w = d[7];
         o[0] = v0;
         o[1] = v1;
+    }
+}
+
+// cec_digest_apply_diffs: keep a live digest array current.  The digest is linear, so a diff
+// that is XORed into an arena (times a coefficient) is folded into the arena's digests as
+//     digests[off >> 12] ^= coef * digest(a unit, zero but for the diff bytes at off & 4095).
+// digest_update_kernel is digest_kernel's reduction over a diff placed in its unit: one wave
+// per tile (a tile never crosses a 4 KiB arena boundary), four waves per workgroup, no LDS,
+// no barrier.
+//   * lane L holds UNIT chunks L, L + 64, L + 128, L + 192.  A chunk that lies inside the
+//     tile is one global_load_dwordx4 when the diff's address is 16-B aligned with the arena
+//     offset (ecalloc's offsets: every chunk of the tile but a ragged last one); a chunk the
+//     tile covers in part, or at any other alignment, is the byte gather over the covered
+//     bytes only; a chunk outside the tile is zero.  Bytes outside the tile are never fetched;
+//   * the wave's 32-byte total (digest_wave_total) is spread over lanes 0..7, one dword each,
+//     multiplied there by the tile's coefficient (pattern [0]: coef[0][j] / tab[0][j] of source
+//     lid j, scalar loads; a tile whose coefficient is 0 returns before it reads anything),
+//   * and XORed into the live digest by ONE wave instruction: a no-return global_atomic_xor
+//     of eight lanes on the 32 contiguous bytes, relaxed, agent scope.  Sixteen 256-byte values
+//     share a unit, so several waves of a launch meet in one digest; XOR commutes, so the
+//     bytes are the same in any order, overlapping extents included.
+struct DigestUpdateArgs {
+    const uint8_t *diffs;    // tiles' src_off count from here
+    uint8_t *digests;        // unit u at digests + 32 * u; 16-B aligned
+    const Tile *tiles;
+    const Pattern *pattern;  // [0]: coef[0][j], tab[0][j] = MATRIX(lid_self, j) for source lid j
+    uint32_t n_tiles;
+};
+
+// Bytes [first, first + cnt) of the 16-byte chunk at base + off (cnt >= 1, first + cnt <= 16);
+// the other bytes read 0.  gather16's scheme: byte b reads the address of the nearest
+// covered byte, so all 16 loads are in bounds and in flight together.
+__device__ inline uint4 gather16_at(const uint8_t *base, uint32_t off, uint32_t first, uint32_t cnt) {
+    uint32_t v[16];
+#pragma unroll
+    for (int b = 0; b < 16; ++b)
+        v[b] = ld8(base, off + min(max(static_cast<uint32_t>(b), first), first + cnt - 1));
+    uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int b = 0; b < 16; ++b) w[b >> 2] |= (static_cast<uint32_t>(b) - first < cnt ? v[b] : 0u) << (8 * (b & 3));
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+__global__ __launch_bounds__(kBlock) void digest_update_kernel(DigestUpdateArgs a) {
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t t = (blockIdx.x << 2) + wave;
+    if (t >= a.n_tiles) return;  // (wave-uniform)
+    const CEC_CONST Tile *tl = as_const(a.tiles) + t;
+    const uint64_t off = tl->off;
+    const uint32_t len = tl->len;
+    const uint32_t src = tl->pattern;
+    const CEC_CONST Pattern *P = as_const(a.pattern);
+    if (P->coef[0][src] == 0) return;  // another shard's diff: nothing read
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t lo = static_cast<uint32_t>(off) & (kTile - 1u), hi = lo + len;  // the tile in its unit
+    // where unit byte 0 would lie in the diffs: only bytes [lo, hi) of it are addressed
+    const uint8_t *unit = a.diffs + tl->src_off - lo;
+    const bool aligned = (reinterpret_cast<uint64_t>(unit) & 15) == 0;
+
+    uint4 c[4];
+    if (aligned && len == kTile) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) c[j] = ld16(unit, (lane + 64u * j) * 16u);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t pos = (lane + 64u * j) * 16u;
+            const uint32_t b0 = max(pos, lo), b1 = min(pos + 16u, hi);  // covered bytes of the chunk
+            c[j] = make_uint4(0, 0, 0, 0);
+            if (b0 < b1) c[j] = aligned && b1 - b0 == 16u ? ld16(unit, pos) : gather16_at(unit, pos, b0 - pos, b1 - b0);
+        }
+    }
+    uint32_t d[8];
+    digest_wave_total(c, lane, d);
+    uint32_t v = 0;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) {
+        const uint32_t total = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(d[w]), 63));
+        v = lane == static_cast<uint32_t>(w) ? total : v;
+    }
+    if (lane < 8) {
+        v = PermEngine::mul(PermEngine::sel(v), P->tab[0][src], nullptr);
+        CEC_GLOBAL uint32_t *o = (CEC_GLOBAL uint32_t *)((uintptr_t)a.digests + (off >> 12) * kDigestBytes) + lane;
+        __hip_atomic_fetch_xor(o, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 

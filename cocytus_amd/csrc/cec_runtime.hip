@@ -319,6 +319,8 @@ struct cec_plan {
     int64_t n_line_tiles = 0;   // full kTile tiles at a 128-B aligned arena offset
     Tile *d_tiles = nullptr;    // from dev_cache() (NULL: the empty plan)
     uint32_t max_pattern = 0;       // largest extent pattern (per-op index validation)
+    uint64_t max_end = 0;           // largest off + len of a non-empty extent (saturating) ...
+    int max_end_ext = -1;           // ... and the first extent that reaches it
     std::vector<Tile> h_tiles;      // kept alive for the async upload
     mutable Tracker uses;           // the streams of the tile upload and of every launch
 };
@@ -353,7 +355,15 @@ CEC_API int cec_plan_create(cec_plan **out, const cec_extent *ext, int n, void *
     if (!p) return fail(CEC_ENOMEM, "cec_plan_create: host allocation");
     p->device = dev;
     p->n_ext = n;
-    for (int e = 0; e < n; ++e) p->max_pattern = std::max(p->max_pattern, ext[e].pattern);
+    for (int e = 0; e < n; ++e) {
+        p->max_pattern = std::max(p->max_pattern, ext[e].pattern);
+        if (!ext[e].len) continue;
+        const uint64_t end = ext[e].off > UINT64_MAX - ext[e].len ? UINT64_MAX : ext[e].off + ext[e].len;
+        if (p->max_end_ext < 0 || end > p->max_end) {
+            p->max_end = end;
+            p->max_end_ext = e;
+        }
+    }
     size_t total_tiles = 0;
     for (int e = 0; e < n; ++e) total_tiles += tiles_of(ext[e].off, ext[e].len);
     p->h_tiles.resize(total_tiles);
@@ -453,6 +463,8 @@ struct WaveTiles {
         n += append_tiles(h + n, off, src_off, len, pattern);
     }
     int waves() const { return static_cast<int>(first.size()); }
+    // Every tile added so far, whatever its wave (for a launch whose tiles may overlap).
+    TileSource all(const Tile *d) const { return TileSource::window(d, h, n); }
     // Wave w's launch, d being the device address of h; n_tiles == 0: nothing to launch.
     TileSource window(int w, const Tile *d) const {
         const size_t lo = first[w], hi = w + 1 < waves() ? first[w + 1] : n;
@@ -611,7 +623,7 @@ static_assert(kFlagSysRelease == CEC_LAUNCH_SYS_RELEASE && kFlagWriteThrough == 
                   kFlagWtTail == CEC_LAUNCH_WT_TAIL, "cec_launch_record::flags");
 
 // The calling thread's last enqueued kernel launch (cec_last_launch).  record_launch is
-// the one place that writes it: launch_combine, scrub_launch and the two digest launches
+// the one place that writes it: launch_combine, scrub_launch and the three digest launches
 // (cec_digest.inc), the library's launch routines, each call it once per kernel they enqueue.
 static thread_local cec_launch_record t_last_launch = {0, -1, 0, 0, -1, -1, 0, 0, 0, 0, 0, kNoWtTail};
 

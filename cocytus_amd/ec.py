@@ -119,6 +119,7 @@ CEC_KERNEL_NARROW, CEC_KERNEL_EXACT, CEC_KERNEL_GENERIC = 0, 1, 2
 CEC_KERNEL_SCRUB = 3  # cec_scrub's read-only kernel
 CEC_KERNEL_DIGEST = 4  # cec_digest's reduction (nt = the arenas of the launch, lt = 0)
 CEC_KERNEL_DIGEST_CHECK = 5  # cec_scrub_digests: the scrub's test, one lane per unit
+CEC_KERNEL_DIGEST_UPDATE = 6  # cec_digest_apply_diffs: one wave per tile into the live digests
 DIGEST_BYTES = 32  # CEC_DIGEST_BYTES: per 4 KiB unit
 CEC_SCRUB_UNLOCATED = -1
 
@@ -224,6 +225,9 @@ _SIGS = {
     "cec_digest_region": ([_i, _pp, _pp, ctypes.c_size_t, _vp], _i),
     "cec_scrub_digests": ([_vp, _i, _i, _ip, _pp, _pp, _vp, _vp], _i),
     "cec_scrub_digests_region": ([_vp, _i, _i, _ip, _pp, _pp, ctypes.c_size_t, _vp], _i),
+    "cec_digest_apply_diffs": ([_i, _i, _ip, _i, _vp, _vp, ctypes.c_uint64, _vp, _vp], _i),
+    "cec_digest_verify_region": ([_vp, _vp, _vp, ctypes.c_size_t, _vp], _i),
+    "cec_drainer_set_digests": ([_vp, _vp, ctypes.c_uint64], _i),
     "cec_cache_get_info": ([ctypes.POINTER(CacheInfo)], _i),
     "cec_last_sync": ([ctypes.POINTER(SyncRecord)], _i),
     "cec_last_launch": ([ctypes.POINTER(LaunchRecord)], _i),
@@ -296,13 +300,10 @@ def lib() -> ctypes.CDLL:
     return L
 
 
-def kernel_code_id(path: str | None = None) -> str | None:
-    """Identity of the library's device code: sha256 (16 hex digits) of its gfx950 code
-    object disassembled (llvm-objdump), one block per kernel sorted by name, addresses
-    and encodings dropped -- so host-only changes and a different link order of the same
-    kernels keep the id, and any change to a kernel's instructions changes it.  Nothing
-    is loaded.  None if the file or llvm-objdump is missing."""
-    import hashlib
+def kernel_disassembly(path: str | None = None) -> dict[str, list[str]] | None:
+    """{kernel symbol: its instructions} of the library's gfx950 code object disassembled
+    (llvm-objdump), addresses and encodings dropped.  Nothing is loaded.  None if the file
+    or llvm-objdump is missing.  (tools/kernel_isa_diff.py compares two builds with it.)"""
     import re
     import shutil
     import subprocess
@@ -332,6 +333,18 @@ def kernel_code_id(path: str | None = None) -> str | None:
             ins = line.split("//")[0].strip()
             if ins:
                 cur.append(ins)
+    return funcs or None
+
+
+def kernel_code_id(path: str | None = None) -> str | None:
+    """Identity of the library's device code: sha256 (16 hex digits) of its gfx950 code
+    object disassembled (kernel_disassembly), one block per kernel sorted by name, addresses
+    and encodings dropped -- so host-only changes and a different link order of the same
+    kernels keep the id, and any change to a kernel's instructions changes it.  Nothing
+    is loaded.  None if the file or llvm-objdump is missing."""
+    import hashlib
+
+    funcs = kernel_disassembly(path)
     if not funcs:
         return None
     h = hashlib.sha256()
@@ -607,6 +620,14 @@ def digest_region(arenas, digests, length: int, stream=None) -> None:
     _check(lib().cec_digest_region(len(arenas), _ptr_array(arenas), _ptr_array(digests), length, _stream(stream)))
 
 
+def digest_apply_diffs(k, m, matrix, lid_self, diffs, digests, n_units: int, plan: Plan, stream=None) -> None:
+    """cec_digest_apply_diffs: fold the plan's diffs (apply_diffs' extents) into the live
+    digest array of lid_self (any lid; n_units units of 32 bytes, 16-byte aligned); async on
+    stream.  Overlapping extents are accepted."""
+    _check(lib().cec_digest_apply_diffs(k, m, _int_array(matrix), lid_self, _ptr(diffs), _ptr(digests), n_units,
+                                        plan.handle, _stream(stream)))
+
+
 def recovery_mask(k: int, m: int, leader_lid: int, connected: Sequence[int]) -> int:
     return lib().cec_recovery_mask(k, m, leader_lid, _int_array(connected))
 
@@ -635,6 +656,11 @@ class Drainer:
         arr = updates if isinstance(updates, ctypes.Array) else host_updates(updates)
         _check(lib().cec_drainer_apply(self._h, arr, len(arr), _ptr(parity), _stream(stream)))
         return lib().cec_drainer_last_launches(self._h)
+
+    def set_digests(self, digests, n_units: int = 0) -> None:
+        """cec_drainer_set_digests: every apply also keeps this live digest array of the parity
+        current (the caller keeps it alive); None detaches."""
+        _check(lib().cec_drainer_set_digests(self._h, _ptr(digests), n_units))
 
     def staging(self):
         """(address, numpy uint8 view) of the drainer's pinned staging area: diffs
@@ -901,6 +927,12 @@ class Scrub:
     def run_digests_region(self, k, m, matrix, data_digests, parity_digests, length: int, stream=None) -> None:
         _check(lib().cec_scrub_digests_region(self._h, k, m, _int_array(matrix), _ptr_array(data_digests),
                                               _ptr_array(parity_digests), length, _stream(stream)))
+
+    def verify_region(self, live, fresh, length: int, stream=None) -> None:
+        """cec_digest_verify_region: a process's own check, its live digests against a fresh
+        digest_region of its arena over [0, length); wait() returns the differing units, whose
+        findings carry lid CEC_SCRUB_UNLOCATED (the lid is the caller's own)."""
+        _check(lib().cec_digest_verify_region(self._h, _ptr(live), _ptr(fresh), length, _stream(stream)))
 
     def wait(self) -> int:
         n = lib().cec_scrub_wait(self._h)

@@ -237,18 +237,33 @@ int cec_drainer_release_stream(cec_drainer *d, void *stream);   /* LIFETIME RULE
  * the later ones not, and a retry would apply the earlier ones twice: the parity arena is
  * then inconsistent in some 4 KiB units of the window's ranges.  Where every arena of the
  * group is on this device, cec_scrub + cec_scrub_repair over those ranges find and rebuild
- * them (below); otherwise the process must stop. */
+ * them (below); otherwise the process must stop -- or, with live digests (LIVE DIGESTS,
+ * below), let cec_scrub_digests over the group's live arrays name the units a lost or
+ * twice-applied diff left wrong.  Attached digests (cec_drainer_set_digests) are then as
+ * uncertain as the arena in the window's units: after units [u0, u0 + n) are rebuilt,
+ * re-base them: cec_digest_region of `arena + 4096 * u0` into `digests + 32 * u0`, len 4096 * n. */
 int cec_drainer_apply(cec_drainer *d, const cec_host_update *updates, int n,
                       uint8_t *parity, void *stream);
 
 /* The checks cec_drainer_apply makes on its updates before it touches anything (src_lid
- * < k, buf non-NULL when len > 0, len <= half the staging area), on the host only: CEC_OK
+ * < k, buf non-NULL when len > 0, len <= half the staging area, and with digests attached
+ * addr + len <= n_units * 4096), on the host only: CEC_OK
  * or CEC_EINVAL.  A caller with side effects per update (the server's recovery fold) runs
  * it first, so that an update the apply would refuse is refused before any of them. */
 int cec_drainer_validate(const cec_drainer *d, const cec_host_update *updates, int n);
 
-/* Launches the last cec_drainer_apply needed (>= 1 when n > 0: overlap waves x rounds). */
+/* Launches the last cec_drainer_apply needed (>= 1 when n > 0: overlap waves x rounds,
+ * plus one per round while digests are attached). */
 int cec_drainer_last_launches(const cec_drainer *d);
+
+/* Attach the parity's live digest array (LIVE DIGESTS, below: device memory, 32 B per 4 KiB
+ * unit of the arena, n_units units, 16-byte aligned; the caller owns it and keeps it alive
+ * while attached).  Every cec_drainer_apply then also folds each round's staged diffs into
+ * it: one cec_digest_apply_diffs launch per round, behind the round's fold launches on the
+ * same stream, over all the round's tiles at once.  digests == NULL detaches: every path
+ * then does exactly what it does without this call.  CEC_EINVAL: a NULL drainer, a
+ * misaligned array, n_units above 2^52. */
+int cec_drainer_set_digests(cec_drainer *d, uint8_t *digests, uint64_t n_units);
 
 /* The drainer's pinned staging area (2 x staging_bytes; *capacity receives its size).
  * A server can receive diffs straight into it (conn_nread of the "rep" payload,
@@ -536,8 +551,26 @@ int cec_scrub_repair(cec_scrub_report *s, int k, int m, const int *matrix, uint8
  *
  * SNAPSHOT RULE: the digests of a group must be taken with every shard at the same stable
  * xid, in the idle loop -- the condition cec_scrub's idle-loop placement already assumes.
- * Out of scope: keeping digests current on each SET (linearity allows
- * digest ^= digest(diff) later); every call here digests the bytes as they are.
+ *
+ * LIVE DIGESTS: a process may keep one digest array of its arena current instead of taking
+ * it anew for every scrub.  The array has cec_digest_region's geometry -- unit u of the
+ * arena at digests + 32 * u, chunk i of unit u = arena bytes [4096 u + 16 i, +16) -- and is
+ * based once with cec_digest_region.  The digest is linear, so every diff that is XORed into
+ * the arena is folded into the array too (cec_digest_apply_diffs; a parity's drainer does it
+ * itself, cec_drainer_set_digests):
+ *     digest(unit after) = digest(unit before) ^ c * digest(the diff, placed where it lands).
+ * A live array equals cec_digest_region of the arena at any quiescent point of the owning
+ * process (no diff applied to one and not yet to the other).  That gives two checks:
+ *   - local, no peer, any time: cec_digest_verify_region(live, a fresh cec_digest_region of
+ *     the own arena).  A mismatch is bit rot or a stray write in that arena;
+ *   - across processes, no arena read: cec_scrub_digests over the shards' live arrays (same
+ *     SNAPSHOT RULE).  It catches what the local check cannot: a lost or twice-applied diff.
+ * An op that writes an arena outside this path -- cec_scrub_repair, the recovery pool's
+ * solves into arenas, cec_diff_update (its fused path does not keep digests), and the units
+ * of a drain window after a CEC_EHIP -- is followed by a re-base of the units it wrote:
+ * cec_digest_region of the one arena `arena + 4096 * u0` into `digests + 32 * u0`, len =
+ * 4096 * n, for units [u0, u0 + n) (to the arena's end for the last, ragged unit); the unit
+ * geometry makes that pointer arithmetic valid.
  *
  * cec_digest: digests[a] + 32 * t = digest of tile t of arenas[a], for n arenas (1..24: a
  * whole group, or a process's own) in one launch; async on `stream`.  Read-only on the
@@ -566,6 +599,42 @@ int cec_scrub_digests(cec_scrub_report *s, int k, int m, const int *matrix,
                       const cec_plan *plan, void *stream);
 int cec_scrub_digests_region(cec_scrub_report *s, int k, int m, const int *matrix,
                              const uint8_t *const *data_digests, const uint8_t *const *parity_digests,
+                             size_t len, void *stream);
+
+/* Fold applied diffs into a live digest array (LIVE DIGESTS above); async on `stream`.
+ * digests: this shard's live array, unit u of the arena at digests + 32 * u (the geometry of
+ * cec_digest_region: chunk i of unit u = arena bytes [4096 u + 16 i, +16)), n_units units.
+ * The plan's extents are those of cec_apply_diffs: `off` the arena offset, `src_off` the
+ * offset into `diffs`, `pattern` the source data lid j.  For every 4 KiB tile of the plan
+ *     digests[off >> 12] ^= MATRIX(lid_self, j) * D,
+ * D = the digest of a 4 KiB unit that is zero but for the tile's diff bytes at in-unit offset
+ * off & 4095.  Any offset and length are accepted (16-byte aligned ones take the wide path).
+ * lid_self is any lid in 0..k+m-1: for a parity the coefficient is cec_apply_diffs'; for a
+ * data lid the matrix row is the identity row, so a data shard folds its own cec_set_diff
+ * output with coefficient 1 and an extent that names another shard contributes nothing.
+ * Tiles whose coefficient is 0 read nothing.  Bytes of `diffs` outside the tiles are never
+ * fetched, and `diffs` is only read.
+ * The totals are accumulated with relaxed agent-scope atomic XORs, because several values
+ * share a unit; XOR commutes, so the result is bit-exact in any order.  For the same reason
+ * this op ACCEPTS plans whose extents overlap: there is no CEC_EOVERLAP here (two extents on
+ * the same bytes fold twice, as applying both diffs to the arena would).  Applying the same
+ * plan twice restores the digests.
+ * Refused with CEC_EINVAL before anything is launched: a bad code or lid_self, NULL diffs,
+ * digests or plan, digests not 16-byte aligned, an extent pattern >= k, a plan of another
+ * device, n_units above 2^52, and an extent that ends beyond n_units * 4096 (the message
+ * names it).  An empty plan launches nothing.  A failed launch (CEC_EHIP) changes no digest.
+ * ENGINE: PERM arithmetic, as cec_digest. */
+int cec_digest_apply_diffs(int k, int m, const int *matrix, int lid_self, const uint8_t *diffs,
+                           uint8_t *digests, uint64_t n_units, const cec_plan *plan, void *stream);
+
+/* A process's check of itself: compare its live array with a fresh cec_digest_region of its
+ * own arena (both device arrays of 32 B per unit over [0, len), 16-byte aligned).  It is
+ * cec_scrub_digests_region with the code k = 1, m = 1, matrix {1, 1}, `fresh` as the data
+ * digests and `live` as the parity's: the syndrome is live ^ fresh.  Same report, same
+ * refusals; cec_scrub_wait returns the differing units and cec_scrub_findings their tile,
+ * off and len.  Every finding's lid is CEC_SCRUB_UNLOCATED (m = 1 never locates): the caller
+ * knows the lid is its own.  cec_scrub_repair does not apply to such a run. */
+int cec_digest_verify_region(cec_scrub_report *s, const uint8_t *live, const uint8_t *fresh,
                              size_t len, void *stream);
 
 /* ---- process-wide caches ----
@@ -624,7 +693,10 @@ enum { CEC_KERNEL_NARROW = 0, CEC_KERNEL_EXACT = 1, CEC_KERNEL_GENERIC = 2,
        CEC_KERNEL_DIGEST = 4 /* cec_digest: nt = the arenas of the launch, lt = 0, acc = CEC_ACC_NONE,
                               * split_shift 0, PERM, flags 0 */,
        CEC_KERNEL_DIGEST_CHECK = 5 /* cec_scrub_digests: nt / lt = the capacities {4,8,16} x {1,2,4},
-                                    * acc = CEC_ACC_ALL, PERM, flags 0 */ };
+                                    * acc = CEC_ACC_ALL, PERM, flags 0 */,
+       CEC_KERNEL_DIGEST_UPDATE = 6 /* cec_digest_apply_diffs and the drainer's digest launch: nt = 1,
+                                     * lt = 0, acc = CEC_ACC_ALL, split_shift 0, PERM, flags 0, grid =
+                                     * ceil(tiles / 4) */ };
 enum { CEC_ACC_NONE = 0, CEC_ACC_ALL = 1, CEC_ACC_ALL_BUT_LAST = 2, CEC_ACC_RUNTIME = 3 };
 enum { CEC_LAUNCH_SYS_RELEASE = 1, CEC_LAUNCH_WRITE_THROUGH = 2,
        CEC_LAUNCH_WT_TAIL = 4 /* non-temporal body, write-through stores from work item wt_from on */ };

@@ -24,6 +24,8 @@
  * ONE cec_drainer_apply (one H2D + one fold launch; overlapping diffs are put in separate
  * waves, XOR accumulation commutes, so the parity bytes equal the sequential loop's).  The
  * server then runs the rest of process_rep_command per xid, without its two GF lines.
+ * A parity that keeps live unit digests attaches them to the drainer once
+ * (cec_drainer_set_digests, cocytus_ec.h): every apply here then keeps them current too.
  */
 #ifndef COCYTUS_DRAIN_H
 #define COCYTUS_DRAIN_H
