@@ -52,7 +52,9 @@ struct Combo {
         uint8_t stream, src, mode;
         int coef[kPatN];
     };
-    std::vector<Out> outs;  // install output (if any) is last
+    // An output that overwrites one of the inputs (the diff-update's install, the fused
+    // finish's R') is last: past kPatL outputs the launches run in order (build_patterns).
+    std::vector<Out> outs;
 
     // One more input: stream `slot`, addressed by the tile's src_off (`by_src`) or its off.
     // Returns the input's index into every output's coef[].  Past kPatN nothing is stored

@@ -303,7 +303,8 @@ CEC_API int cec_recovery_solve(cec_recovery *r, const void *const *peer_residual
 //   R'  = R_or_P ^ c * D                        (kept: cec_recovery_residual)
 //   out = inv[x][self] * R' ^ sum_{j != self} inv[x][j] * C_j
 //       = inv_s * R_or_P ^ (inv_s * c) * D ^ ...  (exact in GF(2^8))
-// Device or pinned buffers are used in place: one launch, in which the kernel reads
+// Device or pinned buffers are used in place: one launch up to three lost shards (1 + n
+// outputs, kPatL a launch: ceil((n + 1) / 4) launches for n lost), in which the kernel reads
 // the peer's bytes and writes the rebuilt bytes over PCIe in both directions at once.
 // Pageable buffers take the two-step path (add_peer, then solve): their cost is the
 // host copy through pinned staging, and a piecewise fused pipeline measured slower
@@ -350,15 +351,18 @@ CEC_API int cec_recovery_finish(cec_recovery *r, int peer, const void *units,
         if (int rc = peer_residual(r, "cec_recovery_finish", peer_residuals, ls.pars[j], tmp, s, &cj)) return rc;
         in_res[j] = cb.in(st.add(cj));
     }
-    Combo::Out &ro = cb.out(st.add(r->residual), kModeWrite);
-    ro.coef[in_d] = c;
-    ro.coef[in_res[self]] = 1;
     for (int x = 0; x < ls.n; ++x) {
         // data[i] = calloc, then += (memcached.c:7913-7922)
         Combo::Out &q = cb.out(st.add(device_view_of(out[ls.lost[x]])), kModeWrite);
         q.coef[in_d] = gf_mul(ls.at(x, self), c);
         for (int j = 0; j < ls.n; ++j) q.coef[in_res[j]] = ls.at(x, j);
     }
+    // R' is stated last: once touched it overwrites the input R, and past kPatL outputs the
+    // combination runs as successive launches -- every rebuilt shard must have read R by then
+    // (build_patterns: an output that overwrites an input of its combination goes last).
+    Combo::Out &ro = cb.out(st.add(r->residual), kModeWrite);
+    ro.coef[in_d] = c;
+    ro.coef[in_res[self]] = 1;
     if (int rc = run_combos_region(dev, st, {cb}, r->nbuf, s)) return rc;
     // Synchronous (cocytus_ec.h): the rebuilt bytes are in out on return, and units /
     // peer residuals may be reused by the caller.

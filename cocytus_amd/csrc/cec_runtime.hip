@@ -791,9 +791,13 @@ static int run_combine(int dev, const Streams &st, const std::vector<Pattern> &p
     return CEC_OK;
 }
 
-// The patterns of launch g of a combo list: outputs [4g, 4g+4) of every combo (an
-// install output is last in `outs`, so it runs in the final launch after every group
-// read old bytes), with the engine's coefficient form (and LDS rows).
+// The patterns of launch g of a combo list: outputs [4g, 4g+4) of every combo, with the
+// engine's coefficient form (and LDS rows).  The launches of one combo run in order on one
+// stream, so no launch may read a stream an earlier launch of the combo wrote: an output
+// that overwrites an input of its own combination is last in `outs` and runs in the final
+// launch, after every group read the old bytes.  Two ops have one: the diff-update's install
+// (the new value over the data shard) and cec_recovery_finish's R' (the new residual over
+// the touched session's residual).
 // This is where a Combo becomes a Pattern, so the Pattern's capacities are enforced here
 // for every caller: at most kPatN inputs, and -- for a caller that launches group g alone
 // (`only_group`: the region multiply, the pool's flush) -- no output past that group, which

@@ -367,7 +367,9 @@ int cec_recovery_solve(cec_recovery *leader, const void *const *peer_residuals,
  * cec_recovery_solve; same bytes, same residual afterwards).  With device or pinned
  * buffers it is ONE pass: the kernel reads the peer's bytes and writes the rebuilt
  * bytes (over PCIe in both directions at once for pinned host memory).  Pageable
- * buffers take the two-step path.  EINVAL if peer is not the last data peer. */
+ * buffers take the two-step path.  Any loss count n up to m: the pass is
+ * ceil((n + 1) / 4) launches (the residual and the n rebuilt shards, four outputs a
+ * launch; one launch up to three losses).  EINVAL if peer is not the last data peer. */
 int cec_recovery_finish(cec_recovery *leader, int peer_lid, const void *units,
                         const void *const *peer_residuals, void *const *out, void *stream);
 
