@@ -26,6 +26,17 @@
 //               O[slot] = inv * R[slot] into the pool's own mapped pinned output O, which
 //             the host reads in place (no arena is written: the caller decides which
 //             units to fill, as fill_completed_recovered_data skips sub_flags == 2)
+//   n losses  a request that loses n >= 2 data lids is led by this pool once the other
+//             n - 1 participating parities' residuals have been given (add_residual: what
+//             recover_units_gather receives into data_from_parity[lid], memcached.c:
+//             4190-4219, and complete_recovery_bottom_half puts into C[], :7881-7888).  They
+//             lie in one more mapped pinned staging G_p per parity lid, at the request's
+//             slots, and the solve is the combination cec_recovery_finish builds:
+//               out[lost_x] = sum_p inv[x][p] * C[p],  C[self] = R[slot], C[p] = G_p[slot]
+//             four shards a launch.  A flush that makes such a request ready (its last
+//             reply or its last residual) solves it in its own launch up to three losses
+//             (R' and the shards are the launch's four outputs); past three the solve's
+//             launches follow the flush's in the same call and read the new R from HBM.
 //   updates   fold_update flushes first, so a queued reply is folded exactly when the
 //             reference would have folded it (before the next parity change), then
 //             R ^= c * diff where the request is touched and the peer has not contributed
@@ -106,7 +117,12 @@ struct cec_recovery_pool {
     // PCIe (no upload ahead of each launch), through the buffer's device alias
     Buf tiles;
     Buf diff;  // pinned mapped staging for diffs
-    Buf out;   // mapped pinned, capacity * kTile (_host solves, on first use)
+    // _host solves: plane x holds the x-th lost lid's rebuilt units at the request's slots;
+    // mapped pinned, capacity * kTile each, on first use
+    Buf out[CEC_MAX_M];
+    // given residuals of the other participating parities (multi-loss requests), by parity
+    // index: mapped pinned, capacity * kTile each, on first use of that parity
+    Buf given[CEC_MAX_M];
     struct Req {
         bool used = false;
         uint32_t mask = 0;
@@ -115,6 +131,8 @@ struct cec_recovery_pool {
         bool touch_pending = false; // the first touch happens at the next flush
         uint32_t contributed = 0;   // data lids applied or queued
         uint32_t queued = 0;        // data lids queued for the next flush
+        uint32_t given = 0;         // parity lids whose residual was given (static: never folded into)
+        bool enqueued = false;      // in queued_ids: a reply or a residual came since the last flush
         bool solved = false;        // rebuilt by a solve, and R has not changed since
         bool solved_host = false;   // ... into out_host (the _host solves)
     };
@@ -123,8 +141,12 @@ struct cec_recovery_pool {
     std::vector<int> slot_owner;  // -1 free
     int cursor = 0;               // next-fit start: O(1) amortised begin for unit-sized requests
     std::vector<int> queued_ids;
-    // The flush patterns seen so far, one per (queued peer set, first touch, lost lid
-    // solved), at most 2^k * 2 * (k+1): key -> index into `tables` (the pool's own).
+    // The flush patterns seen so far: poolbook::flush_key -> index into `tables` (the pool's
+    // own).  One per (queued peer set, first touch) for the requests a flush only folds, at
+    // most 2^k * 2; and for those it also solves one per (queued peer set, first touch, mask,
+    // to_host) -- the mask, not the lost lid alone: it names the parities whose residuals
+    // come in and decides the inverse -- at most 2^(k-n) * 2 * 2 per mask of n <= 3 losses,
+    // C(k,n) * C(m-1,n-1) masks per n (this parity is in every one).
     std::map<uint64_t, int> flush_pat;
     PoolTables tables;
     Tracker uses;  // the streams of its calls (destroy waits for those only)
@@ -223,6 +245,20 @@ static cec_recovery_pool::Req *pool_req(cec_recovery_pool *p, int id) {
     return &p->reqs[id];
 }
 
+// The request has something for the next flush: a reply to fold, or a residual that may
+// have made it ready.
+static void pool_enqueue(cec_recovery_pool *p, int id) {
+    poolbook::enqueue(p->queued_ids, p->reqs[id].enqueued, id);
+}
+
+static poolbook::Req pool_book_req(const cec_recovery_pool *p, int id) {
+    if (!p || id < 0 || id >= static_cast<int>(p->reqs.size()) || !p->reqs[id].used) return {};
+    const cec_recovery_pool::Req &r = p->reqs[id];
+    return {true, r.mask, r.contributed, r.given};
+}
+static_assert(poolbook::kMaxK == CEC_MAX_K && poolbook::kMaxM == CEC_MAX_M && poolbook::kStreams == kMaxStreams &&
+                  poolbook::kInputs == kPatN && poolbook::kOutputs == kPatL, "cec_poolbook.hpp's limits");
+
 CEC_API int cec_recovery_pool_add_peer(cec_recovery_pool *p, int id, int peer, const void *units) {
     cec_recovery_pool::Req *r = pool_req(p, id);
     if (!r || !units || peer < 0 || peer >= p->code.k || !(r->mask & (1u << peer)))
@@ -245,7 +281,7 @@ CEC_API int cec_recovery_pool_add_peer(cec_recovery_pool *p, int id, int peer, c
         r->touch_pending = true;
     }
     r->contributed |= 1u << peer;
-    if (!r->queued) p->queued_ids.push_back(id);
+    pool_enqueue(p, id);
     r->queued |= 1u << peer;
     return CEC_OK;
 }
@@ -283,36 +319,167 @@ CEC_API uint8_t *cec_recovery_pool_staging(cec_recovery_pool *p, int id, int pee
     return p->q[peer].get() + static_cast<size_t>(r->slot) * kTile;
 }
 
+// The staging of parity_lid's given residuals, acquired on its first use (a pool that sees
+// no multi-loss request holds none).  NULL: no such other parity, or no memory.
+static Buf *pool_given_staging(cec_recovery_pool *p, int parity_lid) {
+    if (parity_lid < p->code.k || parity_lid >= p->code.k + p->code.m || parity_lid == p->lid_self) return nullptr;
+    Buf &g = p->given[parity_lid - p->code.k];
+    const size_t bytes = static_cast<size_t>(p->capacity) * kTile;
+    if (!g && !g.acquire_mapped(p->device, bytes)) {
+        (void)fail(CEC_ENOMEM, "recovery pool: %zu bytes of staging for parity %d's residuals", bytes, parity_lid);
+        return nullptr;
+    }
+    return &g;
+}
+
+CEC_API uint8_t *cec_recovery_pool_parity_staging(cec_recovery_pool *p, int id, int parity_lid, size_t *len) {
+    cec_recovery_pool::Req *r = pool_req(p, id);
+    if (!r) {
+        (void)fail(CEC_EINVAL, "cec_recovery_pool_parity_staging: request %d", id);
+        return nullptr;
+    }
+    // only where add_residual would take one: another parity of a multi-loss request's mask
+    // (given already or not) -- nothing is acquired for any other lid or request
+    poolbook::Req view = pool_book_req(p, id);
+    view.given = 0;
+    if (poolbook::check_residual(p->code.k, p->code.m, p->lid_self, view, parity_lid)) {
+        (void)fail(CEC_EINVAL, "cec_recovery_pool_parity_staging: request %d takes no residual of lid %d", id,
+                   parity_lid);
+        return nullptr;
+    }
+    Buf *g = pool_given_staging(p, parity_lid);
+    if (!g) return nullptr;
+    if (len) *len = static_cast<size_t>(r->nunits) * kTile;
+    return g->get() + static_cast<size_t>(r->slot) * kTile;
+}
+
+static const char *const kResidualRefusal[] = {
+    "accepted", "no such request", "the lid is no parity of the request's mask",
+    "the pool's own parity (its residual is the pool's)", "that parity's residual was given before",
+    "a single-loss request takes no residual", "a (request, parity) pair listed twice"};
+
+// The n residuals into their stagings, then -- every copy done -- the bookkeeping: a failed
+// device copy (CEC_EHIP) or staging allocation (CEC_ENOMEM) leaves nothing given or queued.
+static int pool_give(cec_recovery_pool *p, const char *op, const int *ids, const int *lids,
+                     const void *const *residuals, int n) {
+    for (int i = 0; i < n; ++i) {
+        const cec_recovery_pool::Req &r = p->reqs[ids[i]];
+        Buf *g = pool_given_staging(p, lids[i]);
+        if (!g) return CEC_ENOMEM;
+        const size_t off = static_cast<size_t>(r.slot) * kTile, len = static_cast<size_t>(r.nunits) * kTile;
+        uint8_t *const dst = g->get() + off;
+        if (residuals[i] == dst) {
+            // received in place (cec_recovery_pool_parity_staging): nothing to copy
+        } else if (const PtrKind kind = classify(residuals[i]); kind.known && !kind.host && kind.dev) {
+            // device memory: one synchronous copy by the runtime per residual (host memory of
+            // any kind: memcpy)
+            int dev;
+            if (int rc = current_device(&dev)) return rc;
+            if (dev != p->device) return fail(CEC_EINVAL, "pool of device %d used on %d", p->device, dev);
+            if (hipError_t e = hipMemcpy(dst, kind.dev, len, hipMemcpyDefault); e != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(CEC_EHIP, "%s: copy of residual %d: %s", op, i, hipGetErrorString(e));
+            }
+        } else {
+            memcpy(dst, residuals[i], len);
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        p->reqs[ids[i]].given |= 1u << lids[i];
+        pool_enqueue(p, ids[i]);  // its last residual may make it ready: the next flush looks
+    }
+    return CEC_OK;
+}
+
+CEC_API int cec_recovery_pool_add_residuals(cec_recovery_pool *p, const int *ids, const int *parity_lids,
+                                            const void *const *residuals, int n) {
+    if (!p || n < 0 || (n > 0 && (!ids || !parity_lids || !residuals)))
+        return fail(CEC_EINVAL, "cec_recovery_pool_add_residuals: bad args");
+    for (int i = 0; i < n; ++i)
+        if (!residuals[i]) return fail(CEC_EINVAL, "cec_recovery_pool_add_residuals: residual %d is NULL", i);
+    int bad = 0;
+    if (poolbook::Refusal why = poolbook::check_residuals(
+            p->code.k, p->code.m, p->lid_self, ids, parity_lids, n, [p](int id) { return pool_book_req(p, id); }, &bad))
+        return fail(CEC_EINVAL, "cec_recovery_pool_add_residuals: residual %d (request %d, parity %d): %s", bad,
+                    ids[bad], parity_lids[bad], kResidualRefusal[why]);
+    return pool_give(p, "cec_recovery_pool_add_residuals", ids, parity_lids, residuals, n);
+}
+
+CEC_API int cec_recovery_pool_add_residual(cec_recovery_pool *p, int id, int parity_lid, const void *residual) {
+    if (!p || !residual) return fail(CEC_EINVAL, "cec_recovery_pool_add_residual: bad args");
+    if (poolbook::Refusal why =
+            poolbook::check_residual(p->code.k, p->code.m, p->lid_self, pool_book_req(p, id), parity_lid))
+        return fail(CEC_EINVAL, "cec_recovery_pool_add_residual: request %d, parity %d: %s", id, parity_lid,
+                    kResidualRefusal[why]);
+    return pool_give(p, "cec_recovery_pool_add_residual", &id, &parity_lid, &residual, 1);
+}
+
+CEC_API int cec_recovery_pool_ready(const cec_recovery_pool *p, int id) {
+    return p && poolbook::ready(p->code.k, p->lid_self, pool_book_req(p, id)) ? 1 : 0;
+}
+
 // Fold every queued reply in one launch.  With `out` (k arenas by data lid), a request
 // that this flush completes and that is a single loss led by this parity is solved in
 // the same pass: out[lost][off] = inv * R'[slot], from the same inputs (exact in GF(2^8),
 // as cec_recovery_finish).  Returns the requests folded; *solved gets those solved.
-static int pool_out_host(cec_recovery_pool *p) {  // the _host solves' output, on first use
+static int pool_out_host(cec_recovery_pool *p, int planes) {  // the _host solves' output planes, on first use
     const size_t bytes = static_cast<size_t>(p->capacity) * kTile;
-    if (!p->out && !p->out.acquire_mapped(p->device, bytes))
-        return fail(CEC_ENOMEM, "recovery pool: %zu bytes of host output", bytes);
+    for (int x = 0; x < planes; ++x)
+        if (!p->out[x] && !p->out[x].acquire_mapped(p->device, bytes))
+            return fail(CEC_ENOMEM, "recovery pool: %zu bytes of host output (plane %d)", bytes, x);
     return CEC_OK;
 }
 
-// The streams of a flush.  Its patterns outlive the call (PoolTables is append-only), so the
-// slots are a function of k alone, the same in every flush: P, R, the k reply stagings, the
-// k arenas of a flush_solve (empty without `out`), out_host (empty unless to_host).
+// The streams of a flush.  Its patterns outlive the call (PoolTables is append-only) with
+// the slots baked in, so the slots are a function of (k, m) alone, the same in every flush:
+// poolbook::FlushSlots states the layout and its bound (42 of kMaxStreams = 48 at k = 16,
+// m = 8), and this fills it in that order.  A buffer not acquired yet leaves its slot empty;
+// no pattern of the launch names it (launch_combine checks).
 struct FlushStreams {
     Streams st;
-    int parity, residual, q[CEC_MAX_K], out[CEC_MAX_K], out_host;
-    FlushStreams(const cec_recovery_pool *p, uint8_t *const *o, bool to_host)
-        : parity(st.add(p->parity)), residual(st.add(p->residual.get())) {
-        for (int j = 0; j < p->code.k; ++j) q[j] = st.add(p->q[j].alias());
-        for (int j = 0; j < p->code.k; ++j) out[j] = st.add(o ? o[j] : nullptr);
-        out_host = st.add(to_host ? p->out.alias() : nullptr);
+    poolbook::FlushSlots at;
+    FlushStreams(const cec_recovery_pool *p, uint8_t *const *o, bool to_host) : at{p->code.k, p->code.m} {
+        const int k = p->code.k, m = p->code.m;
+        bool ok = st.add(p->parity) == at.parity() && st.add(p->residual.get()) == at.residual();
+        for (int j = 0; j < k; ++j) ok &= st.add(p->q[j].alias()) == at.reply(j);
+        for (int j = 0; j < k; ++j)  // arenas by data lid, or host planes by lost ordinal
+            ok &= st.add(to_host ? (j < CEC_MAX_M && p->out[j] ? p->out[j].alias() : nullptr) : o ? o[j] : nullptr) ==
+                  at.out(j);
+        for (int q = 0; q < m; ++q) ok &= st.add(p->given[q] ? p->given[q].alias() : nullptr) == at.given(k + q);
+        if (!ok || st.n != at.count()) st.refused = true;  // (the layout and this constructor disagree)
     }
 };
 
-// A single loss led by parity lid_self (the pool solves no other): its lost data lid, else -1.
-static int pool_single_loss(const cec_recovery_pool *p, uint32_t mask) {
+// The lost data lids of a mask, ascending (as C[] / data[] are ordered, memcached.c:7911-7922).
+static int pool_lost_lids(const cec_recovery_pool *p, uint32_t mask, int *lost) {
+    int n = 0;
+    for (int j = 0; j < p->code.k; ++j)
+        if (!(mask & (1u << j))) lost[n++] = j;
+    return n;
+}
+
+// One combination that rebuilds the n lost shards of `mask` from C[self] = sum_i a[i] *
+// (input i of c, i < n_self: R itself, or the inputs of a flush's R') and the given
+// residuals, which it adds as inputs from the slots given_slot(parity lid):
+//   shard x = sum_p inv[x][p] * C[p]      (memcached.c:7907-7922; exact in GF(2^8))
+// into out_slot(x, lost lid), slot-addressed if by_src.  Appends n outputs to c.
+template <class GivenSlot, class OutSlot>
+static int pool_solve_combo(const cec_recovery_pool *p, uint32_t mask, Combo &c, const int *a, int n_self,
+                            GivenSlot given_slot, OutSlot out_slot, bool by_src) {
     Loss ls;
-    if (Loss::of(p->code, mask, "recovery pool", &ls, false) || ls.n != 1 || ls.pars[0] != p->lid_self) return -1;
-    return ls.lost[0];
+    if (int rc = Loss::of(p->code, mask, "recovery pool", &ls)) return rc;
+    const int self = ls.index_of_parity(p->lid_self);
+    if (self < 0) return fail(CEC_EINVAL, "recovery pool: mask 0x%x does not name this parity", mask);
+    int in_given[CEC_MAX_M];
+    for (int r = 0; r < ls.n; ++r)
+        if (r != self) in_given[r] = c.in(given_slot(ls.pars[r]), true);
+    for (int x = 0; x < ls.n; ++x) {
+        Combo::Out &q = c.out(out_slot(x, ls.lost[x]), kModeWrite, by_src);
+        for (int i = 0; i < n_self; ++i) q.coef[i] = gf_mul(ls.at(x, self), a[i]);
+        for (int r = 0; r < ls.n; ++r)
+            if (r != self) q.coef[in_given[r]] = ls.at(x, r);
+    }
+    return CEC_OK;
 }
 
 // The pool's mapped diff staging, grown to hold `len` bytes (idle: every earlier call
@@ -323,87 +490,133 @@ static int pool_diff_staging(cec_recovery_pool *p, size_t len, const char *op) {
     return CEC_OK;
 }
 
-// to_host: the solves go to out_host at the request's slots instead of out[lost].
+static int pool_solve_run(cec_recovery_pool *p, int dev, std::vector<int> ids, uint8_t *const *out, bool to_host,
+                          hipStream_t s);
+
+// to_host: the solves go to the host planes at the request's slots instead of out[lost].
 static int pool_flush(cec_recovery_pool *p, uint8_t *const *out, bool to_host, void *stream, int *solved) {
     if (solved) *solved = 0;
     if (p->queued_ids.empty()) return 0;
     int dev;
     if (int rc = current_device(&dev)) return rc;
     if (dev != p->device) return fail(CEC_EINVAL, "pool of device %d used on %d", p->device, dev);
-    if (to_host) {
-        if (int rc = pool_out_host(p)) return rc;
-    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     UseNote note_{p->uses, s};
     const int k = p->code.k;
+    // What the pass does with each queued request: fold its replies (kFold), fold and solve in
+    // the same launch (kFused: ready, at most three losses -- R' and the shards are the
+    // launch's four outputs), fold now and solve behind the launch (`later`: ready, four
+    // losses or more), or nothing (a residual came, and the request is not ready or the pass
+    // does not solve).
+    enum { kNothing, kFold, kFused };
+    std::vector<char> plan(p->queued_ids.size(), kNothing);
+    std::vector<int> later;
+    int planes = 0;
+    for (size_t x = 0; x < p->queued_ids.size(); ++x) {
+        const int id = p->queued_ids[x];
+        const cec_recovery_pool::Req &r = p->reqs[id];
+        if (r.queued || r.touch_pending) plan[x] = kFold;
+        if (!(out || to_host) || !cec_recovery_pool_ready(p, id)) continue;
+        int lost[CEC_MAX_K];
+        const int n = pool_lost_lids(p, r.mask, lost);
+        bool have_out = true;  // (a lost lid's arena not given: folded only, as ever)
+        for (int i = 0; i < n && !to_host; ++i) have_out &= out[lost[i]] != nullptr;
+        if (!have_out) continue;
+        if (n <= poolbook::kFusedLosses) {
+            plan[x] = kFused;
+            planes = std::max(planes, n);
+        } else {
+            later.push_back(id);
+        }
+    }
+    if (to_host) {
+        if (int rc = pool_out_host(p, planes)) return rc;
+    }
     const FlushStreams fs(p, out, to_host);
     const int engine = op_engine(false);
     if (p->tables.engine != engine) {  // the table's coefficient form is per engine
         p->tables.reset(dev, engine);
         p->flush_pat.clear();
     }
-    // one pattern per (queued peer set, first touch, lost lid solved or none), from the
-    // pool's persistent table
+    // one pattern per poolbook::flush_key, from the pool's persistent table
     std::vector<char> used;
     size_t nt = 0;
-    int n_solved = 0;
-    for (int id : p->queued_ids) {
-        cec_recovery_pool::Req &r = p->reqs[id];
-        int lost = -1;
-        if ((out || to_host) && cec_recovery_pool_complete(p, id)) {
-            lost = pool_single_loss(p, r.mask);
-            if (lost >= 0 && !to_host && !out[lost]) lost = -1;
-        }
-        const uint64_t key = r.queued | (r.touch_pending ? 1ull << 31 : 0ull) |
-                             (static_cast<uint64_t>(lost + 1) << 32) |
-                             (to_host && lost >= 0 ? 1ull << 40 : 0ull);
+    int folded = 0;
+    for (size_t x = 0; x < p->queued_ids.size(); ++x) {
+        if (plan[x] == kNothing) continue;
+        const cec_recovery_pool::Req &r = p->reqs[p->queued_ids[x]];
+        const bool fused = plan[x] == kFused, folds = r.queued || r.touch_pending;
+        const uint64_t key = poolbook::flush_key(r.queued, r.touch_pending, fused, r.mask, to_host);
         auto it = p->flush_pat.find(key);
         if (it == p->flush_pat.end()) {
             Combo c;
-            Combo::Out &o = c.out(fs.residual, kModeWrite, true);  // R, slot-addressed
-            // P, arena-addressed: the first-touch copy (recovery.c:79-82); else R itself
-            o.coef[r.touch_pending ? c.in(fs.parity) : c.in(fs.residual, true)] = 1;
+            // R' = sum_i a[i] * input i.  P, arena-addressed: the first-touch copy
+            // (recovery.c:79-82); else R itself, slot-addressed
+            int a[kPatN] = {};
+            a[r.touch_pending ? c.in(fs.at.parity()) : c.in(fs.at.residual(), true)] = 1;
             for (int j = 0; j < k; ++j)
-                if (r.queued & (1u << j)) o.coef[c.in(fs.q[j], true)] = p->code.at(p->lid_self, j);  // recovery.c:91-93
-            if (lost >= 0) {  // the leader's bottom half in the same pass (memcached.c:7907-7922)
-                const int inv = gf_inv(p->code.at(p->lid_self, lost));
-                // the lost lid's arena, arena offset; or out_host, slot-addressed
-                Combo::Out &q = to_host ? c.out(fs.out_host, kModeWrite, true) : c.out(fs.out[lost], kModeWrite);
-                for (int i = 0; i < c.n_in; ++i) q.coef[i] = gf_mul(inv, c.outs[0].coef[i]);
+                if (r.queued & (1u << j)) a[c.in(fs.at.reply(j), true)] = p->code.at(p->lid_self, j);  // recovery.c:91-93
+            const int n_self = c.n_in;  // (<= k - n + 1; the given residuals make it at most k)
+            if (folds) {  // (a residual-only pass leaves R as it is)
+                Combo::Out &o = c.out(fs.at.residual(), kModeWrite, true);
+                for (int i = 0; i < n_self; ++i) o.coef[i] = a[i];
             }
-            // (<= 2 outputs: one pattern; refused before the table or the key map change)
+            if (fused) {  // the leader's bottom half in the same pass (memcached.c:7907-7922)
+                // host plane x, slot-addressed; or the lost lid's arena, arena offset
+                if (int rc = pool_solve_combo(
+                        p, r.mask, c, a, n_self, [&](int lid) { return fs.at.given(lid); },
+                        [&](int ord, int lid) { return fs.at.out(to_host ? ord : lid); }, to_host))
+                    return rc;
+            }
+            // (<= 4 outputs: one pattern; refused before the table or the key map change)
             const int at = static_cast<int>(p->tables.pats.size());
             if (int rc = build_patterns({c}, 0, engine, p->tables.pats, p->tables.rows, true)) return rc;
             it = p->flush_pat.emplace(key, at).first;
         }
         used.resize(p->tables.pats.size(), 0);
         used[it->second] = 1;
+        if (nt + r.nunits > static_cast<size_t>(p->capacity))  // (cannot happen: the queue holds an id once)
+            return fail(CEC_EINVAL, "recovery pool: a flush of more units than the tile buffer; not launched");
         nt += append_tiles(p->tiles.get<Tile>() + nt, static_cast<uint64_t>(r.ub) * kTile,
                            static_cast<uint64_t>(r.slot) * kTile, static_cast<uint32_t>(r.nunits) * kTile,
                            static_cast<uint32_t>(it->second));
-        if (lost >= 0) {
+        folded += folds;  // (a request only solved by this pass is not counted as folded)
+    }
+    if (nt) {
+        used.resize(p->tables.pats.size(), 0);
+        if (int rc = p->tables.sync(s)) return rc;
+        // (the pool's tile buffer: whole 4 KiB units on 4 KiB offsets)
+        if (int rc = launch_combine(dev, fs.st,
+                                    Tables{p->tables.d.get(), p->tables.cap_pats, p->tables.pats.data(), &used},
+                                    launch_shape(p->tables.pats, &used), engine == CEC_ENGINE_LDS,
+                                    TileSource::whole_units(p->tiles.alias<Tile>(), nt), s))
+            return rc;
+        HIP_TRY(hipGetLastError());
+        // tile buffer and staging reusable; rebuilt shards visible if out is host memory
+        if (int rc = stream_wait(s, to_host || (out && any_host_memory(out, k)))) return rc;
+    }
+    int n_solved = 0;
+    for (size_t x = 0; x < p->queued_ids.size(); ++x) {
+        cec_recovery_pool::Req &r = p->reqs[p->queued_ids[x]];
+        r.queued = 0;
+        r.touch_pending = false;
+        r.enqueued = false;
+        if (plan[x] == kFused) {
             r.solved = true;
             r.solved_host = to_host;
             ++n_solved;
         }
     }
-    used.resize(p->tables.pats.size(), 0);
-    if (int rc = p->tables.sync(s)) return rc;
-    // (the pool's tile buffer: whole 4 KiB units on 4 KiB offsets)
-    if (int rc = launch_combine(dev, fs.st, Tables{p->tables.d.get(), p->tables.cap_pats, p->tables.pats.data(), &used},
-                                launch_shape(p->tables.pats, &used), engine == CEC_ENGINE_LDS,
-                                TileSource::whole_units(p->tiles.alias<Tile>(), nt), s))
-        return rc;
-    HIP_TRY(hipGetLastError());
-    // tile buffer and staging reusable; rebuilt shards visible if out is host memory
-    if (int rc = stream_wait(s, to_host || (out && any_host_memory(out, k)))) return rc;
-    const int folded = static_cast<int>(p->queued_ids.size());
-    for (int id : p->queued_ids) {
-        p->reqs[id].queued = 0;
-        p->reqs[id].touch_pending = false;
-    }
     p->queued_ids.clear();
     if (solved) *solved = n_solved;
+    // Four losses and more: R' is in HBM and the launch above is complete (the tile buffer is
+    // free again), so the solve reads the new R as an explicit solve would -- the hazard of
+    // cec_recovery_finish's R' (an output over an input of a split combination) does not arise.
+    if (!later.empty()) {
+        const int n_later = static_cast<int>(later.size());
+        if (int rc = pool_solve_run(p, dev, std::move(later), out, to_host, s)) return rc;
+        if (solved) *solved = n_solved + n_later;
+    }
     return folded;
 }
 
@@ -426,12 +639,16 @@ CEC_API int cec_recovery_pool_flush_solve_host(cec_recovery_pool *p, void *strea
     return rc < 0 ? rc : solved;
 }
 
-CEC_API const uint8_t *cec_recovery_pool_output(const cec_recovery_pool *p, int id, size_t *len) {
+CEC_API const uint8_t *cec_recovery_pool_output_lost(const cec_recovery_pool *p, int id, int x, size_t *len) {
     if (!p || id < 0 || id >= static_cast<int>(p->reqs.size()) || !p->reqs[id].used) return nullptr;
     const cec_recovery_pool::Req &r = p->reqs[id];
-    if (!r.solved || !r.solved_host) return nullptr;
+    if (!r.solved || !r.solved_host || x < 0 || x >= poolbook::n_lost(p->code.k, r.mask) || !p->out[x]) return nullptr;
     if (len) *len = static_cast<size_t>(r.nunits) * kTile;
-    return p->out.get() + static_cast<size_t>(r.slot) * kTile;
+    return p->out[x].get() + static_cast<size_t>(r.slot) * kTile;
+}
+
+CEC_API const uint8_t *cec_recovery_pool_output(const cec_recovery_pool *p, int id, size_t *len) {
+    return cec_recovery_pool_output_lost(p, id, 0, len);
 }
 
 CEC_API int cec_recovery_pool_solved(const cec_recovery_pool *p, int id) {
@@ -608,7 +825,111 @@ CEC_API int cec_recovery_pool_fold_updates(cec_recovery_pool *p, const cec_host_
     return total_units;
 }
 
-// to_host: O[slot] = inv * R[slot] into out_host instead of out[lost][off].
+// The solve of checked requests (live, ready, distinct, their outputs there), the flush done:
+// ceil(n_max / 4) launches for the largest loss count among them.
+//   to_host: plane x [slot] instead of out[lost_x][off].
+// The first k combinations are the single losses, one per lost data lid x (out[x] = inv * R,
+// pattern index = x), always all k of them: one table per pool and engine in the coefficient
+// cache, whatever the mix of single-loss requests (`used` picks the kernel shape).  Each
+// multi-loss mask listed adds one combination behind them.  The requests are listed by
+// descending loss count, so launch g (outputs 4g .. 4g+3) runs over a prefix of the tile
+// buffer: those that lose more than 4g shards.
+static int pool_solve_run(cec_recovery_pool *p, int dev, std::vector<int> ids, uint8_t *const *out, bool to_host,
+                          hipStream_t s) {
+    const int k = p->code.k;
+    auto losses = [&](int id) { return poolbook::n_lost(k, p->reqs[id].mask); };
+    std::stable_sort(ids.begin(), ids.end(), [&](int a, int b) { return losses(a) > losses(b); });
+    const int n_max = losses(ids.front());
+    if (to_host) {
+        if (int rc = pool_out_host(p, n_max)) return rc;
+    }
+    Streams st;
+    const int s_residual = st.add(p->residual.get());
+    int s_plane[CEC_MAX_M], s_given[CEC_MAX_M], s_arena[CEC_MAX_K];
+    std::fill(s_plane, s_plane + CEC_MAX_M, -1);
+    std::fill(s_given, s_given + CEC_MAX_M, -1);
+    if (to_host) s_plane[0] = st.add(p->out[0].alias());
+    for (int x = 0; x < k && !to_host; ++x) s_arena[x] = st.add(out[x]);
+    std::vector<Combo> combos(k);
+    for (int x = 0; x < k; ++x) {
+        Combo &c = combos[x];
+        const int in_r = c.in(s_residual, true);  // R, slot-addressed
+        // plane 0, slot-addressed; or the lost lid's arena, arena offset
+        Combo::Out &o = to_host ? c.out(s_plane[0], kModeWrite, true) : c.out(s_arena[x], kModeWrite);
+        const int cx = p->code.at(p->lid_self, x);
+        o.coef[in_r] = cx ? gf_inv(cx) : 0;  // memcached.c:7907-7922, n_lost = 1
+    }
+    std::map<uint32_t, int> combo_of;  // multi-loss mask -> its combination
+    size_t nt = 0;
+    std::vector<size_t> tiles_upto(poolbook::solve_launches(n_max), 0);  // launch g's prefix of the tiles
+    for (int id : ids) {
+        const cec_recovery_pool::Req &r = p->reqs[id];
+        const int n = losses(id);
+        int pattern;
+        if (n == 1) {
+            int lost[CEC_MAX_K];
+            (void)pool_lost_lids(p, r.mask, lost);
+            pattern = lost[0];
+        } else {
+            auto it = combo_of.find(r.mask);
+            if (it == combo_of.end()) {
+                Combo c;
+                const int one = 1;
+                c.in(s_residual, true);  // C[self] = R, slot-addressed
+                if (int rc = pool_solve_combo(
+                        p, r.mask, c, &one, 1,
+                        [&](int lid) {  // (given: checked ready)
+                            int &slot = s_given[lid - k];
+                            return slot >= 0 ? slot : (slot = st.add(p->given[lid - k].alias()));
+                        },
+                        [&](int ord, int lid) {
+                            if (!to_host) return s_arena[lid];
+                            return s_plane[ord] >= 0 ? s_plane[ord] : (s_plane[ord] = st.add(p->out[ord].alias()));
+                        },
+                        to_host))
+                    return rc;
+                it = combo_of.emplace(r.mask, static_cast<int>(combos.size())).first;
+                combos.push_back(c);
+            }
+            pattern = it->second;
+        }
+        if (nt + r.nunits > static_cast<size_t>(p->capacity))  // (cannot happen once ids are distinct)
+            return fail(CEC_EINVAL, "cec_recovery_pool_solve: more units than the tile buffer");
+        nt += append_tiles(p->tiles.get<Tile>() + nt, static_cast<uint64_t>(r.ub) * kTile,
+                           static_cast<uint64_t>(r.slot) * kTile, static_cast<uint32_t>(r.nunits) * kTile,
+                           static_cast<uint32_t>(pattern));
+        for (int g = 0; g < poolbook::solve_launches(n); ++g) tiles_upto[g] = nt;
+    }
+    const int engine = op_engine(false);
+    for (size_t g = 0; g < tiles_upto.size(); ++g) {
+        // the combinations launch g's tiles name: those listed that have an output past 4g
+        std::vector<char> used(combos.size(), 0);
+        for (int id : ids) {
+            const cec_recovery_pool::Req &r = p->reqs[id];
+            if (losses(id) == 1) {
+                int lost[CEC_MAX_K];
+                (void)pool_lost_lids(p, r.mask, lost);
+                used[lost[0]] = g == 0;
+            } else if (losses(id) > static_cast<int>(g) * kPatL) {
+                used[combo_of[r.mask]] = 1;
+            }
+        }
+        std::vector<Pattern> pats;
+        std::vector<uint8_t> rows;
+        if (int rc = build_patterns(combos, g, engine, pats, rows)) return rc;
+        // (whole 4 KiB units on 4 KiB offsets, as the flush's)
+        if (int rc = run_combine(dev, st, pats, rows, TileSource::whole_units(p->tiles.alias<Tile>(), tiles_upto[g]), s,
+                                 &used, engine))
+            return rc;
+    }
+    if (int rc = stream_wait(s, to_host || any_host_memory(out, k))) return rc;
+    for (int id : ids) {
+        p->reqs[id].solved = true;
+        p->reqs[id].solved_host = to_host;
+    }
+    return CEC_OK;
+}
+
 static int pool_solve(cec_recovery_pool *p, const int *ids, int n, uint8_t *const *out, bool to_host,
                       void *stream) {
     if (!p || n < 0 || (n > 0 && (!ids || (!out && !to_host))))
@@ -618,54 +939,24 @@ static int pool_solve(cec_recovery_pool *p, const int *ids, int n, uint8_t *cons
     if (int rc = current_device(&dev)) return rc;
     if (dev != p->device) return fail(CEC_EINVAL, "pool of device %d used on %d", p->device, dev);
     if (int rc = cec_recovery_pool_flush(p, stream); rc < 0) return rc;
-    if (to_host) {
-        if (int rc = pool_out_host(p)) return rc;
-    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     UseNote note_{p->uses, s};
-    const int k = p->code.k;
-    // One pattern per lost data lid x, always all k of them (out[x] = inv * R, pattern
-    // index = x): one table per pool and engine in the coefficient cache, whatever the
-    // mix of requests (`used` picks the kernel shape).
-    Streams st;
-    const int s_residual = st.add(p->residual.get()), s_out_host = to_host ? st.add(p->out.alias()) : -1;
-    std::vector<Combo> combos(k);
-    std::vector<char> used(k, 0);
-    for (int x = 0; x < k; ++x) {
-        Combo &c = combos[x];
-        const int in_r = c.in(s_residual, true);  // R, slot-addressed
-        // out_host, slot-addressed; or the lost lid's arena, arena offset
-        Combo::Out &o = to_host ? c.out(s_out_host, kModeWrite, true) : c.out(st.add(out[x]), kModeWrite);
-        const int cx = p->code.at(p->lid_self, x);
-        o.coef[in_r] = cx ? gf_inv(cx) : 0;  // memcached.c:7907-7922, n_lost = 1
-    }
-    size_t nt = 0;
     std::vector<char> listed(p->reqs.size(), 0);
     for (int x = 0; x < n; ++x) {
         cec_recovery_pool::Req *r = pool_req(p, ids[x]);
         if (!r || !cec_recovery_pool_complete(p, ids[x]))
             return fail(CEC_EINVAL, "cec_recovery_pool_solve: request %d missing or incomplete", ids[x]);
         if (listed[ids[x]]++) return fail(CEC_EINVAL, "cec_recovery_pool_solve: request %d listed twice", ids[x]);
-        const int lost = pool_single_loss(p, r->mask);
-        if (lost < 0)
-            return fail(CEC_EINVAL, "cec_recovery_pool_solve: request %d is not a single-loss request "
-                                    "led by this parity (use cec_recovery sessions)", ids[x]);
-        if (!to_host && !out[lost]) return fail(CEC_EINVAL, "cec_recovery_pool_solve: out[%d] is NULL", lost);
-        used[lost] = 1;
-        if (nt + r->nunits > static_cast<size_t>(p->capacity))  // (cannot happen once ids are distinct)
-            return fail(CEC_EINVAL, "cec_recovery_pool_solve: more units than the tile buffer");
-        nt += append_tiles(p->tiles.get<Tile>() + nt, static_cast<uint64_t>(r->ub) * kTile,
-                           static_cast<uint64_t>(r->slot) * kTile, static_cast<uint32_t>(r->nunits) * kTile,
-                           static_cast<uint32_t>(lost));
+        if (!cec_recovery_pool_ready(p, ids[x]))
+            return fail(CEC_EINVAL, "cec_recovery_pool_solve: request %d loses %d shards and not every other "
+                                    "participating parity's residual has been given (cec_recovery_pool_add_residual)",
+                        ids[x], poolbook::n_lost(p->code.k, r->mask));
+        int lost[CEC_MAX_K];
+        const int nl = pool_lost_lids(p, r->mask, lost);
+        for (int i = 0; i < nl && !to_host; ++i)
+            if (!out[lost[i]]) return fail(CEC_EINVAL, "cec_recovery_pool_solve: out[%d] is NULL", lost[i]);
     }
-    // (whole 4 KiB units on 4 KiB offsets, as the flush's)
-    if (int rc = run_combos(dev, st, combos, TileSource::whole_units(p->tiles.alias<Tile>(), nt), s, &used)) return rc;
-    if (int rc = stream_wait(s, to_host || any_host_memory(out, p->code.k))) return rc;
-    for (int x = 0; x < n; ++x) {
-        p->reqs[ids[x]].solved = true;
-        p->reqs[ids[x]].solved_host = to_host;
-    }
-    return CEC_OK;
+    return pool_solve_run(p, dev, std::vector<int>(ids, ids + n), out, to_host, s);
 }
 
 CEC_API int cec_recovery_pool_solve(cec_recovery_pool *p, const int *ids, int n, uint8_t *const *out,
@@ -695,6 +986,10 @@ CEC_API int cec_recovery_pool_end(cec_recovery_pool *p, int id) {
     if (r->queued) {  // a reply still queued: fold it first, it may share a tile list
         if (int rc = cec_recovery_pool_flush(p, nullptr); rc < 0) return rc;
     }
+    // Still in the queue with nothing to fold (a residual came since the last flush): taken
+    // out, or the id -- reused by the next begin, which clears `enqueued` -- would be queued
+    // a second time and its tiles appended twice.
+    poolbook::dequeue(p->queued_ids, r->enqueued, id);
     for (int s = r->slot; s < r->slot + r->nunits; ++s) p->slot_owner[s] = -1;
     r->used = false;
     p->free_ids.push_back(id);

@@ -30,6 +30,7 @@
 #include "../../include/reed_sol.h"
 #include "cec_hostplan.hpp"
 #include "cec_kernels.hpp"
+#include "cec_poolbook.hpp"
 #include "gf256.hpp"
 
 #define CEC_API extern "C" __attribute__((visibility("default")))

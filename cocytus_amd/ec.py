@@ -206,6 +206,11 @@ _SIGS = {
     "cec_recovery_pool_output": ([_vp, _i, ctypes.POINTER(ctypes.c_size_t)], _vp),
     "cec_recovery_pool_staging": ([_vp, _i, _i, ctypes.POINTER(ctypes.c_size_t)], _vp),
     "cec_recovery_pool_complete": ([_vp, _i], _i),
+    "cec_recovery_pool_parity_staging": ([_vp, _i, _i, ctypes.POINTER(ctypes.c_size_t)], _vp),
+    "cec_recovery_pool_add_residual": ([_vp, _i, _i, _vp], _i),
+    "cec_recovery_pool_add_residuals": ([_vp, _ip, _ip, _pp, _i], _i),
+    "cec_recovery_pool_ready": ([_vp, _i], _i),
+    "cec_recovery_pool_output_lost": ([_vp, _i, _i, ctypes.POINTER(ctypes.c_size_t)], _vp),
     "cec_recovery_pool_fold_update": ([_vp, _i, ctypes.c_uint64, _vp, _u32, _vp], _i),
     "cec_recovery_pool_fold_updates": ([_vp, _vp, _i, _ip, _vp], _i),
     "cec_recovery_pool_solve": ([_vp, _ip, _i, _pp, _vp], _i),
@@ -827,15 +832,44 @@ class RecoveryPool:
         ids = (ctypes.c_int * len(rids))(*rids)
         _check(lib().cec_recovery_pool_solve_host(self._h, ids, len(rids), _stream(stream)))
 
-    def output(self, rid: int):
-        """numpy uint8 view of rid's rebuilt units after a _host solve, or None."""
+    def output(self, rid: int, x: int = 0):
+        """numpy uint8 view of the rebuilt units of rid's x-th lost data lid (ascending) after
+        a _host solve, or None."""
         import numpy as np
 
         n = ctypes.c_size_t()
-        addr = lib().cec_recovery_pool_output(self._h, rid, ctypes.byref(n))
+        if x == 0:  # (the call every build has: an earlier one under A/B measurement too)
+            addr = lib().cec_recovery_pool_output(self._h, rid, ctypes.byref(n))
+        else:
+            addr = lib().cec_recovery_pool_output_lost(self._h, rid, x, ctypes.byref(n))
         if not addr:
             return None
         return np.ctypeslib.as_array((ctypes.c_uint8 * n.value).from_address(addr))
+
+    def parity_staging(self, rid: int, parity_lid: int):
+        """(address, numpy uint8 view) where parity_lid's residual for rid may be received in place."""
+        import numpy as np
+
+        n = ctypes.c_size_t()
+        addr = lib().cec_recovery_pool_parity_staging(self._h, rid, parity_lid, ctypes.byref(n))
+        if not addr:  # the library's own error: a request / lid that takes no residual, or no memory
+            msg = (lib().cec_last_error() or b"").decode(errors="replace")
+            raise CecError(CEC_ENOMEM if "bytes of staging" in msg else CEC_EINVAL, msg)
+        return addr, np.ctypeslib.as_array((ctypes.c_uint8 * n.value).from_address(addr))
+
+    def add_residual(self, rid: int, parity_lid: int, residual) -> None:
+        """residual: host / device buffer, or the address from parity_staging() (no copy)."""
+        ptr = residual if isinstance(residual, int) else _host_or_dev(residual)
+        _check(lib().cec_recovery_pool_add_residual(self._h, rid, parity_lid, ptr))
+
+    def add_residuals(self, ids, parity_lids=None, residuals=None) -> None:
+        """n residuals in one call (cec_recovery_pool_add_residuals): lists of request ids,
+        parity lids and buffers / staging addresses, or one pool_replies() tuple built ahead."""
+        ia, pa, ua, n = ids if parity_lids is None else pool_replies(ids, parity_lids, residuals)
+        _check(lib().cec_recovery_pool_add_residuals(self._h, ia, pa, ua, n))
+
+    def ready(self, rid: int) -> bool:
+        return bool(lib().cec_recovery_pool_ready(self._h, rid))
 
     def solved(self, rid: int) -> bool:
         return bool(lib().cec_recovery_pool_solved(self._h, rid))

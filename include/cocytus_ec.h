@@ -379,8 +379,15 @@ int cec_recovery_finish(cec_recovery *leader, int peer_lid, const void *units,
  * every in-flight request's residual in one HBM buffer: replies are queued with a
  * host memcpy into per-peer pinned staging, and cec_recovery_pool_flush folds all of
  * them in ONE launch (first-touch parity copy fused, recovery.c:61-96).  The leader
- * solves any number of complete single-loss requests in one launch into the lost
- * lids' arenas (memcached.c:7842-7922).  Same bytes as the reference chain. */
+ * solves any number of ready requests, of any loss count n up to m, into the lost lids'
+ * arenas (memcached.c:7842-7922): single losses in one launch, n losses in ceil(n / 4).
+ * A request that loses n >= 2 data lids is ready once it is complete and the other n - 1
+ * participating parities' residuals have been given (cec_recovery_pool_add_residual: what
+ * recover_units_gather receives into data_from_parity[lid], memcached.c:4190-4219).  Same
+ * bytes as the reference chain.
+ * Every call that launches ends synchronously.  A call that fails with CEC_EHIP or
+ * CEC_ENOMEM before its launch leaves the pool's bookkeeping as it was: queued replies
+ * stay queued, nothing is marked given or solved. */
 typedef struct cec_recovery_pool cec_recovery_pool;
 
 int cec_recovery_pool_create(cec_recovery_pool **out, int k, int m, const int *matrix, int lid_self,
@@ -401,11 +408,44 @@ int cec_recovery_pool_add_peers(cec_recovery_pool *pool, const int *ids, const i
 /* Where peer peer_lid's reply for request id may be received in place (pinned, mapped;
  * *len bytes): add_peer on this pointer copies nothing. */
 uint8_t *cec_recovery_pool_staging(cec_recovery_pool *pool, int id, int peer_lid, size_t *len);
-/* Fold every queued reply in one launch; returns the requests folded (>= 0). */
+/* Where parity peer parity_lid's residual for request id may be received in place (pinned,
+ * mapped; *len bytes): add_residual on this pointer copies nothing.  One staging buffer per
+ * other parity lid, capacity x 4 KiB, acquired on the first use of that lid (a pool that
+ * never sees a multi-loss request holds none).  NULL, with nothing acquired: no such
+ * request, a single-loss request, or a lid that is not another parity of the request's
+ * mask; NULL also when there is no memory (cec_last_error tells which). */
+uint8_t *cec_recovery_pool_parity_staging(cec_recovery_pool *pool, int id, int parity_lid, size_t *len);
+/* The residual of participating parity parity_lid for multi-loss request id (its units x
+ * 4 KiB; host memory, device memory, or the parity_staging pointer): C[p] of the leader's
+ * solve.  Static once given: later fold_updates do not touch it, as the reference never
+ * touches data_from_parity.  CEC_EINVAL: an id that is not live, a lid that is not a
+ * parity of the request's mask, the pool's own lid, a parity given twice, a single-loss
+ * request (it takes none).  The request goes into the next flush, which solves it if this
+ * made it ready.  The copy is made before any bookkeeping changes: CEC_EHIP / CEC_ENOMEM
+ * leave nothing given and nothing queued.  Host memory of any kind (pageable, pinned,
+ * registered) is copied with memcpy; device memory with one synchronous copy per residual
+ * -- receive into cec_recovery_pool_parity_staging where the rate matters.  A request
+ * ended (cec_recovery_pool_end) before the next flush leaves the queue with it. */
+int cec_recovery_pool_add_residual(cec_recovery_pool *pool, int id, int parity_lid, const void *residual);
+/* The same for n residuals in one call: every entry is checked as add_residual checks it
+ * (and no (request, parity) pair twice) before any is queued, CEC_EINVAL queues nothing;
+ * then every copy is made before any entry is marked given, so CEC_EHIP / CEC_ENOMEM queue
+ * nothing either. */
+int cec_recovery_pool_add_residuals(cec_recovery_pool *pool, const int *ids, const int *parity_lids,
+                                    const void *const *residuals, int n);
+/* 1 when cec_recovery_pool_complete(id) holds and every other participating parity's
+ * residual has been given: the request can be solved.  A single loss: == complete. */
+int cec_recovery_pool_ready(const cec_recovery_pool *pool, int id);
+/* Fold every queued reply in one launch; returns the requests folded (>= 0): those with a
+ * reply queued, not those a residual alone put into the pass. */
 int cec_recovery_pool_flush(cec_recovery_pool *pool, void *stream);
-/* The same launch also solves every request it completes that is a single loss led by
- * this parity: out[lost lid] (k device arenas by data lid, arena-addressed) =
- * inv * residual.  Returns the requests solved; cec_recovery_pool_solved tells which. */
+/* The same call also solves every queued request that it makes ready -- by its last reply or
+ * by its last residual: out[lost lid] (k device arenas by data lid, arena-addressed) =
+ * sum_p inv[x][p] * C[p], C[self] the new residual.  Up to three losses in the flush's own
+ * launch (the residual and the shards are its four outputs); requests of n >= 4 losses are
+ * folded by that launch and solved by ceil(n_max / 4) launches behind it, which read the
+ * new residual from device memory.  A pass with nothing to fold has no fold launch.
+ * Returns the requests solved; cec_recovery_pool_solved tells which. */
 int cec_recovery_pool_flush_solve(cec_recovery_pool *pool, uint8_t *const *out, void *stream);
 /* 1 while the request's rebuilt bytes are current: a solve (fused or explicit) wrote them
  * and no fold_update has changed its residual since (a lost lid's diff, recovery.c:116-120,
@@ -422,20 +462,26 @@ int cec_recovery_pool_fold_update(cec_recovery_pool *pool, int peer_lid, uint64_
  * wave (flushes first).  units[i] (optional) = update i's units folded; returns their sum. */
 int cec_recovery_pool_fold_updates(cec_recovery_pool *pool, const cec_host_update *u, int n, int *units,
                                    void *stream);
-/* Leader, single loss: out[lost lid] (k device arenas by data lid, arena-addressed) =
- * inv * residual for every listed complete request, one launch (flushes first). */
+/* Leader: out[lost lid] (k device arenas by data lid, arena-addressed) = sum_p inv[x][p] *
+ * C[p] for every listed ready request (flushes first): one launch for single losses,
+ * ceil(n_max / 4) for the largest loss count listed.  CEC_EINVAL (nothing solved) if a
+ * listed request is not ready. */
 int cec_recovery_pool_solve(cec_recovery_pool *pool, const int *ids, int n, uint8_t *const *out,
                             void *stream);
 /* For a server whose recovery state stays in host memory (integration/
  * cocytus_recovery_pool.c): the same two solves, but into the pool's own mapped pinned
  * output at each request's slots instead of an arena, so no unit the caller has not
  * chosen is written (fill_completed_recovered_data skips sub_flags == 2 units,
- * memcached.c:7967-8000).  The bytes are fenced for the host when the call returns. */
+ * memcached.c:7967-8000): plane x holds the x-th lost data lid's units, lost lids
+ * ascending (as C[] / data[] are ordered, memcached.c:7911-7922); planes past the first
+ * are acquired on first use.  The bytes are fenced for the host when the call returns. */
 int cec_recovery_pool_flush_solve_host(cec_recovery_pool *pool, void *stream);
 int cec_recovery_pool_solve_host(cec_recovery_pool *pool, const int *ids, int n, void *stream);
 /* Request id's rebuilt bytes (*len = its units x 4 KiB) after a _host solve, while
  * cec_recovery_pool_solved(id) holds; NULL otherwise.  Valid until the request ends. */
 const uint8_t *cec_recovery_pool_output(const cec_recovery_pool *pool, int id, size_t *len);
+/* The same for the x-th lost data lid of the request (x = 0: cec_recovery_pool_output). */
+const uint8_t *cec_recovery_pool_output_lost(const cec_recovery_pool *pool, int id, int x, size_t *len);
 /* Non-leader: copy request id's residual (its units x 4 KiB) to dst (host or device). */
 int cec_recovery_pool_residual(cec_recovery_pool *pool, int id, void *dst, void *stream);
 /* recovery_req_remove: release the request's units. */

@@ -29,7 +29,8 @@ struct rq_state {
     int want;   /* a solve is queued */
     int solved; /* the queued solve ran */
     int n_lost;
-    int on_pool; /* single loss led by this parity: solved by the pool into its output */
+    int on_pool; /* led by this parity (any loss count): solved by the pool into its output */
+    int given;   /* the other parities' residuals were handed to the pool (once: they are static) */
     const struct recovery_queue_item *it;
     char *own[32]; /* the other masks' data[x], malloc'd by the flush */
 };
@@ -132,7 +133,7 @@ int cocytus_rpool_begin(cocytus_rpool *g, struct recovery *r, const struct recov
         if (id < 0) return id;
         st->id = id;
     }
-    st->want = st->solved = st->n_lost = st->on_pool = 0;
+    st->want = st->solved = st->n_lost = st->on_pool = st->given = 0;
     st->it = rqit;
     return CEC_OK;
 }
@@ -311,11 +312,29 @@ int cocytus_rpool_solve(cocytus_rpool *g, struct recovery *r, const struct recov
             return CEC_EINVAL;
         }
     }
+    /* A mask that names this parity is led by the pool: C[self] is its residual, in HBM, and
+     * the other parities' residuals (recover_units_gather's data_from_parity[lid],
+     * memcached.c:4190-4219) go into its parity staging here -- no copy where the reply was
+     * received into cec_recovery_pool_parity_staging.  The next flush solves the request in
+     * its one launch. */
+    const int on_pool = st->id >= 0;
+    if (on_pool && n > 1 && !st->given) {
+        int ids[32], lids[32], ng = 0;
+        const void *res[32];
+        for (int p = 0; p < n; ++p) {
+            if (pars[p] == g->self) continue;
+            ids[ng] = st->id;
+            lids[ng] = pars[p];
+            res[ng++] = rqit->data_from_parity[pars[p]];
+        }
+        if ((rc = cec_recovery_pool_add_residuals(g->pool, ids, lids, res, ng))) return rc;
+        st->given = 1;
+    }
     free_own(st);
     st->want = 1;
     st->solved = 0;
     st->n_lost = n;
-    st->on_pool = n == 1 && pars[0] == g->self;
+    st->on_pool = on_pool;
     st->it = rqit;
     g->want[g->n_want++] = (int)(st - g->q);
     *n_out = n;
@@ -324,12 +343,11 @@ int cocytus_rpool_solve(cocytus_rpool *g, struct recovery *r, const struct recov
 
 int cocytus_rpool_pending(const cocytus_rpool *g) { return g ? g->n_want : 0; }
 
-/* The masks the pool does not solve: data[x] = sum_p inv[x][p] * C[p] over host buffers,
- * C[self] read back from the pool, all of them in one batch. */
+/* The masks the pool does not lead (start_fast_recovery's: this parity is not in them, every
+ * C[] comes from a peer): data[x] = sum_p inv[x][p] * C[p] over host buffers, all of them in
+ * one batch. */
 static int solve_on_host(cocytus_rpool *g) {
-    int nj = 0, rc = CEC_OK, n_cself = 0;
-    char **cself = calloc((size_t)g->n_want + 1, sizeof *cself); /* this parity's C, one per request */
-    if (!cself) return CEC_ENOMEM;
+    int nj = 0, rc = CEC_OK;
     for (int w = 0; w < g->n_want && !rc; ++w) {
         struct rq_state *st = &g->q[g->want[w]];
         if (st->on_pool) continue;
@@ -342,21 +360,8 @@ static int solve_on_host(cocytus_rpool *g) {
             break;
         }
         const char *C[32];
-        for (int p = 0; p < n && !rc; ++p) {
-            if (pars[p] != g->self) {
-                C[p] = it->data_from_parity[pars[p]];
-                continue;
-            }
-            char *b = malloc(nbuf); /* memcached.c:7856-7864: this parity's units */
-            if (!b) {
-                rc = CEC_ENOMEM;
-                break;
-            }
-            cself[n_cself++] = b;
-            rc = cec_recovery_pool_residual(g->pool, st->id, b, g->stream);
-            C[p] = b;
-        }
-        if (rc || (rc = grow((void **)&g->jobs, &g->cap_jobs, nj + n * n, sizeof *g->jobs))) break;
+        for (int p = 0; p < n; ++p) C[p] = it->data_from_parity[pars[p]];
+        if ((rc = grow((void **)&g->jobs, &g->cap_jobs, nj + n * n, sizeof *g->jobs))) break;
         for (int x = 0; x < n && !rc; ++x)
             if (!(st->own[x] = malloc(nbuf))) rc = CEC_ENOMEM;
         for (int x = 0; x < n && !rc; ++x)
@@ -371,14 +376,13 @@ static int solve_on_host(cocytus_rpool *g) {
             }
     }
     if (!rc && nj) rc = cec_region_multiply_batch(g->jobs, nj, g->stream);
-    for (int i = 0; i < n_cself; ++i) free(cself[i]);
-    free(cself);
     return rc;
 }
 
 int cocytus_rpool_flush(cocytus_rpool *g) {
     if (!g) return CEC_EINVAL;
-    /* one launch: every queued reply folded, every single-loss request it completes solved */
+    /* one launch: every queued reply folded, every request the pass made ready solved (up to
+     * three losses; more take the solve's launches behind it in the same call) */
     int rc = cec_recovery_pool_flush_solve_host(g->pool, g->stream);
     if (rc < 0) return rc;
     int ids[1024], n = 0;
@@ -407,6 +411,6 @@ const char *cocytus_rpool_data(const cocytus_rpool *g, const struct recovery *r,
                                int x) {
     const struct rq_state *st = state_of((cocytus_rpool *)g, r, rqit);
     if (!st || !st->solved || x < 0 || x >= st->n_lost) return NULL;
-    if (st->on_pool) return (const char *)cec_recovery_pool_output(g->pool, st->id, NULL);
+    if (st->on_pool) return (const char *)cec_recovery_pool_output_lost(g->pool, st->id, x, NULL);
     return st->own[x];
 }

@@ -94,15 +94,18 @@ int cocytus_rpool_residual(cocytus_rpool *g, struct recovery *r, const struct re
 /* complete_recovery_bottom_half (memcached.c:7842-7922), queued for the next flush: *n_out
  * = the lost data lids.  C = this parity's residual (if in the mask) and
  * rqit->data_from_parity for the other parities of the mask (keep them until the flush).
- * A single loss led by this parity is solved in the flush's own launch; any other mask
- * through one cec_region_multiply_batch after it. */
+ * A mask that names this parity, whatever its loss count, is led by the pool: the other
+ * parities' residuals are handed to it here (cec_recovery_pool_add_residuals; no copy for a
+ * reply received into cec_recovery_pool_parity_staging) and the flush solves it in its own
+ * launch.  A mask without this parity (start_fast_recovery) goes through one
+ * cec_region_multiply_batch after it. */
 int cocytus_rpool_solve(cocytus_rpool *g, struct recovery *r, const struct recovery_queue_item *rqit, int *n_out);
 /* Fold every queued reply and run every queued solve.  Returns the solves run (>= 0). */
 int cocytus_rpool_flush(cocytus_rpool *g);
 /* After the flush that ran rqit's solve: data[x] of the bottom half (the x-th lost data lid,
  * units x UNITSIZE bytes), for fill_completed_recovered_data or the scatter send
  * (memcached.c:7935-7962).  Valid until cocytus_rpool_end; NULL before the solve ran, and
- * for a single loss solved in the pool also once a later fold has changed its residual (a
+ * for a request solved in the pool also once a later fold has changed its residual (a
  * lost lid's SET: read the bytes right after the flush, as the bottom half does). */
 const char *cocytus_rpool_data(const cocytus_rpool *g, const struct recovery *r, const struct recovery_queue_item *rqit,
                                int x);
