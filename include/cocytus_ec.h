@@ -511,9 +511,13 @@ int cec_recovery_pool_active(const cec_recovery_pool *pool);
  *
  * ASSUMPTION: a located lid is exact when at most one lid is corrupt in the tile.  With
  * two or more the verdict is CEC_SCRUB_UNLOCATED or, improbably, a wrong lid, as with any
- * syndrome decoder.  m = 1 detects but never locates.  The location rests on the MDS
- * property of the matrices reed_sol_big_vandermonde_distribution_matrix returns: non-zero
- * parity coefficients whose ratios between two parity rows differ from column to column.
+ * syndrome decoder.  One such case is deterministic: where m mod 4 = 1 (m = 5) the last
+ * parity is alone in its launch and rules out nothing, so a tile with one corrupt data lid
+ * and that parity corrupt as well is reported as the data lid; the repair is correct for
+ * that lid, and the next scrub finds the parity.  m = 1 detects but never locates.  The
+ * location rests on the MDS property of the matrices
+ * reed_sol_big_vandermonde_distribution_matrix returns: non-zero parity coefficients whose
+ * ratios between two parity rows differ from column to column.
  * The scrub over digests (cec_scrub_digests, below) adds one limit of its own: corruption
  * of three or more 16-byte chunks of a tile in one byte column can cancel in the digest --
  * errors (1, 2, 3) * v in chunks 1, 2, 3 do -- and is then not seen at all; random
