@@ -2,7 +2,9 @@
 // Included by cec_runtime.hip after cec_recovery.inc; not a separate TU.  Every buffer
 // is a Buf (cec_cache.inc); fold_updates takes its waves from colour_intervals
 // (cec_hostplan.hpp), its launch windows from WaveTiles (cec_runtime.hip) and its
-// failure guard from InFlight (cec_cache.inc).
+// failure guard from InFlight (cec_cache.inc).  Which request owns which slots, what is
+// queued, ready or solved and what a flush does with whom is poolbook::Book's
+// (cec_poolbook.hpp, no device); here are the buffers, combinations, tiles and launches.
 //
 // The idle recoverer (idle_event_handler, memcached.c:5712-5734) issues one 4 KiB unit
 // per request (do_recovery(NULL, s, s)) with up to TOO_MANY_RECOVERY = 85 in flight
@@ -106,11 +108,9 @@ struct PoolTables {
 
 struct cec_recovery_pool {
     int device = -1;
-    int lid_self = 0;
     std::vector<int> matrix;
     Code code;  // over `matrix`
     const uint8_t *parity = nullptr;  // this parity's arena (device)
-    int capacity = 0;                 // units
     Buf residual;      // device, capacity * kTile
     Buf q[CEC_MAX_K];  // per data lid: pinned, mapped, capacity * kTile
     // capacity tiles (one flush / solve), mapped pinned: the kernel reads them in place over
@@ -123,24 +123,7 @@ struct cec_recovery_pool {
     // given residuals of the other participating parities (multi-loss requests), by parity
     // index: mapped pinned, capacity * kTile each, on first use of that parity
     Buf given[CEC_MAX_M];
-    struct Req {
-        bool used = false;
-        uint32_t mask = 0;
-        int ub = 0, nunits = 0, slot = 0;
-        bool touched = false;       // first touch done or queued
-        bool touch_pending = false; // the first touch happens at the next flush
-        uint32_t contributed = 0;   // data lids applied or queued
-        uint32_t queued = 0;        // data lids queued for the next flush
-        uint32_t given = 0;         // parity lids whose residual was given (static: never folded into)
-        bool enqueued = false;      // in queued_ids: a reply or a residual came since the last flush
-        bool solved = false;        // rebuilt by a solve, and R has not changed since
-        bool solved_host = false;   // ... into out_host (the _host solves)
-    };
-    std::vector<Req> reqs;
-    std::vector<int> free_ids;    // ended request ids, reused LIFO
-    std::vector<int> slot_owner;  // -1 free
-    int cursor = 0;               // next-fit start: O(1) amortised begin for unit-sized requests
-    std::vector<int> queued_ids;
+    poolbook::Book book;  // the requests, their slots and the queue; k, m, this parity's lid, the capacity
     // The flush patterns seen so far: poolbook::flush_key -> index into `tables` (the pool's
     // own).  One per (queued peer set, first touch) for the requests a flush only folds, at
     // most 2^k * 2; and for those it also solves one per (queued peer set, first touch, mask,
@@ -151,7 +134,6 @@ struct cec_recovery_pool {
     PoolTables tables;
     Tracker uses;  // the streams of its calls (destroy waits for those only)
 };
-
 
 CEC_API int cec_recovery_pool_destroy(cec_recovery_pool *p) {
     if (!p) return CEC_OK;
@@ -181,10 +163,8 @@ CEC_API int cec_recovery_pool_create(cec_recovery_pool **out, int k, int m, cons
     cec_recovery_pool *p = new (std::nothrow) cec_recovery_pool;
     if (!p) return fail(CEC_ENOMEM, "cec_recovery_pool_create: host allocation");
     p->device = dev;
-    p->lid_self = lid_self;
     p->code = Code::owned(p->matrix, k, m, matrix);
     p->parity = parity_arena;
-    p->capacity = capacity_units;
     const size_t bytes = static_cast<size_t>(capacity_units) * kTile;
     bool ok = p->residual.acquire(dev_cache(), dev, bytes) && p->tiles.acquire_mapped(dev, capacity_units * sizeof(Tile));
     for (int j = 0; j < k && ok; ++j) ok = p->q[j].acquire_mapped(dev, bytes);
@@ -192,80 +172,33 @@ CEC_API int cec_recovery_pool_create(cec_recovery_pool **out, int k, int m, cons
         cec_recovery_pool_destroy(p);
         return fail(CEC_ENOMEM, "cec_recovery_pool_create: %d units of residual and staging", capacity_units);
     }
-    p->slot_owner.assign(capacity_units, -1);
+    p->book = poolbook::Book(k, m, lid_self, capacity_units);
     p->tables.dev = dev;
     *out = p;
     return CEC_OK;
 }
 
+static_assert(poolbook::kMaxK == CEC_MAX_K && poolbook::kMaxM == CEC_MAX_M && poolbook::kStreams == kMaxStreams &&
+                  poolbook::kInputs == kPatN && poolbook::kOutputs == kPatL && poolbook::kUnit == kTile,
+              "cec_poolbook.hpp's limits");
+
+static const poolbook::Req *pool_find(const cec_recovery_pool *p, int id) { return p ? p->book.find(id) : nullptr; }
+
 CEC_API int cec_recovery_pool_begin(cec_recovery_pool *p, uint32_t mask, int unit_begin, int unit_end) {
-    if (!p || unit_begin < 0 || unit_end < unit_begin || !(mask & (1u << p->lid_self)) ||
-        !mask_ok(p->code.k, p->code.m, mask))
+    const int id = p ? p->book.begin(mask, unit_begin, unit_end) : -poolbook::kBadArgs;
+    if (id == -poolbook::kBadArgs)
         return fail(CEC_EINVAL, "cec_recovery_pool_begin: bad mask 0x%x / units [%d, %d]", mask, unit_begin,
                     unit_end);
     const int n = unit_end - unit_begin + 1;
-    if (n > p->capacity) return fail(CEC_EFULL, "cec_recovery_pool_begin: %d units > capacity", n);
-    // next fit from the cursor, wrapping once: requests end roughly in begin order, so
-    // the free units are usually right at the cursor
-    int slot = -1;
-    for (int step = 0, run = 0, s = p->cursor; step < p->capacity + n; ++step, ++s) {
-        if (s == p->capacity) {
-            s = 0;
-            run = 0;  // a run may not wrap around the end of the buffer
-        }
-        run = p->slot_owner[s] < 0 ? run + 1 : 0;
-        if (run == n) {
-            slot = s - n + 1;
-            break;
-        }
-    }
-    if (slot < 0) return fail(CEC_EFULL, "cec_recovery_pool_begin: no %d free contiguous units", n);
-    p->cursor = (slot + n) % p->capacity;
-    int id;
-    if (!p->free_ids.empty()) {
-        id = p->free_ids.back();
-        p->free_ids.pop_back();
-    } else {
-        id = static_cast<int>(p->reqs.size());
-        p->reqs.emplace_back();
-    }
-    cec_recovery_pool::Req &r = p->reqs[id];
-    r = cec_recovery_pool::Req{};
-    r.used = true;
-    r.mask = mask;
-    r.ub = unit_begin;
-    r.nunits = n;
-    r.slot = slot;
-    for (int s = slot; s < slot + n; ++s) p->slot_owner[s] = id;
+    if (id == -poolbook::kTooLarge) return fail(CEC_EFULL, "cec_recovery_pool_begin: %d units > capacity", n);
+    if (id < 0) return fail(CEC_EFULL, "cec_recovery_pool_begin: no %d free contiguous units", n);
     return id;
 }
 
-static cec_recovery_pool::Req *pool_req(cec_recovery_pool *p, int id) {
-    if (!p || id < 0 || id >= static_cast<int>(p->reqs.size()) || !p->reqs[id].used) return nullptr;
-    return &p->reqs[id];
-}
-
-// The request has something for the next flush: a reply to fold, or a residual that may
-// have made it ready.
-static void pool_enqueue(cec_recovery_pool *p, int id) {
-    poolbook::enqueue(p->queued_ids, p->reqs[id].enqueued, id);
-}
-
-static poolbook::Req pool_book_req(const cec_recovery_pool *p, int id) {
-    if (!p || id < 0 || id >= static_cast<int>(p->reqs.size()) || !p->reqs[id].used) return {};
-    const cec_recovery_pool::Req &r = p->reqs[id];
-    return {true, r.mask, r.contributed, r.given};
-}
-static_assert(poolbook::kMaxK == CEC_MAX_K && poolbook::kMaxM == CEC_MAX_M && poolbook::kStreams == kMaxStreams &&
-                  poolbook::kInputs == kPatN && poolbook::kOutputs == kPatL, "cec_poolbook.hpp's limits");
-
-CEC_API int cec_recovery_pool_add_peer(cec_recovery_pool *p, int id, int peer, const void *units) {
-    cec_recovery_pool::Req *r = pool_req(p, id);
-    if (!r || !units || peer < 0 || peer >= p->code.k || !(r->mask & (1u << peer)))
-        return fail(CEC_EINVAL, "cec_recovery_pool_add_peer: request %d / peer %d", id, peer);
-    if (r->contributed & (1u << peer))
-        return fail(CEC_EINVAL, "cec_recovery_pool_add_peer: peer %d already applied (recovery.c:75)", peer);
-    const size_t off = static_cast<size_t>(r->slot) * kTile, len = static_cast<size_t>(r->nunits) * kTile;
+// A checked reply into the peer's staging at the request's slots, then noted.
+static int pool_take_reply(cec_recovery_pool *p, int id, int peer, const void *units) {
+    const poolbook::Req &r = p->book.reqs[id];
+    const size_t off = static_cast<size_t>(r.slot) * kTile, len = static_cast<size_t>(r.nunits) * kTile;
     uint8_t *const q = p->q[peer].get() + off;
     if (units == q) {
         // received in place (cec_recovery_pool_staging): nothing to copy
@@ -276,14 +209,16 @@ CEC_API int cec_recovery_pool_add_peer(cec_recovery_pool *p, int id, int peer, c
     } else {
         memcpy(q, units, len);
     }
-    if (!r->touched) {
-        r->touched = true;
-        r->touch_pending = true;
-    }
-    r->contributed |= 1u << peer;
-    pool_enqueue(p, id);
-    r->queued |= 1u << peer;
+    p->book.note_reply(id, peer);
     return CEC_OK;
+}
+
+CEC_API int cec_recovery_pool_add_peer(cec_recovery_pool *p, int id, int peer, const void *units) {
+    const poolbook::Refusal why = p ? p->book.check_reply(id, peer, units) : poolbook::kNoReply;
+    if (why == poolbook::kNoReply)
+        return fail(CEC_EINVAL, "cec_recovery_pool_add_peer: request %d / peer %d", id, peer);
+    if (why) return fail(CEC_EINVAL, "cec_recovery_pool_add_peer: peer %d already applied (recovery.c:75)", peer);
+    return pool_take_reply(p, id, peer, units);
 }
 
 // An event-loop pass's replies in one call: every (ids[i], peers[i]) checked as add_peer
@@ -292,39 +227,31 @@ CEC_API int cec_recovery_pool_add_peers(cec_recovery_pool *p, const int *ids, co
                                         const void *const *units, int n) {
     if (!p || n < 0 || (n > 0 && (!ids || !peers || !units)))
         return fail(CEC_EINVAL, "cec_recovery_pool_add_peers: bad args");
-    std::vector<std::pair<int, int>> seen;
-    seen.reserve(n);
-    for (int i = 0; i < n; ++i) {
-        const cec_recovery_pool::Req *r = pool_req(p, ids[i]);
-        const int peer = peers[i];
-        if (!r || !units[i] || peer < 0 || peer >= p->code.k || !(r->mask & (1u << peer)))
-            return fail(CEC_EINVAL, "cec_recovery_pool_add_peers: reply %d: request %d / peer %d", i, ids[i], peer);
-        if (r->contributed & (1u << peer))
-            return fail(CEC_EINVAL, "cec_recovery_pool_add_peers: reply %d: peer %d already applied (recovery.c:75)",
-                        i, peer);
-        seen.emplace_back(ids[i], peer);
-    }
-    std::sort(seen.begin(), seen.end());
-    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
-        return fail(CEC_EINVAL, "cec_recovery_pool_add_peers: a (request, peer) pair listed twice");
-    for (int i = 0; i < n; ++i)
-        if (int rc = cec_recovery_pool_add_peer(p, ids[i], peers[i], units[i])) return rc;  // (HIP copy only)
+    int i = 0;
+    const poolbook::Refusal why = p->book.check_replies(ids, peers, units, n, &i);
+    if (why == poolbook::kNoReply)
+        return fail(CEC_EINVAL, "cec_recovery_pool_add_peers: reply %d: request %d / peer %d", i, ids[i], peers[i]);
+    if (why == poolbook::kApplied)
+        return fail(CEC_EINVAL, "cec_recovery_pool_add_peers: reply %d: peer %d already applied (recovery.c:75)", i,
+                    peers[i]);
+    if (why) return fail(CEC_EINVAL, "cec_recovery_pool_add_peers: a (request, peer) pair listed twice");
+    for (i = 0; i < n; ++i)
+        if (int rc = pool_take_reply(p, ids[i], peers[i], units[i])) return rc;  // (HIP copy only)
     return CEC_OK;
 }
 
 CEC_API uint8_t *cec_recovery_pool_staging(cec_recovery_pool *p, int id, int peer, size_t *len) {
-    cec_recovery_pool::Req *r = pool_req(p, id);
+    const poolbook::Req *r = pool_find(p, id);
     if (!r || peer < 0 || peer >= p->code.k) return nullptr;
     if (len) *len = static_cast<size_t>(r->nunits) * kTile;
     return p->q[peer].get() + static_cast<size_t>(r->slot) * kTile;
 }
 
 // The staging of parity_lid's given residuals, acquired on its first use (a pool that sees
-// no multi-loss request holds none).  NULL: no such other parity, or no memory.
+// no multi-loss request holds none), for another parity of a mask (checked).  NULL: no memory.
 static Buf *pool_given_staging(cec_recovery_pool *p, int parity_lid) {
-    if (parity_lid < p->code.k || parity_lid >= p->code.k + p->code.m || parity_lid == p->lid_self) return nullptr;
     Buf &g = p->given[parity_lid - p->code.k];
-    const size_t bytes = static_cast<size_t>(p->capacity) * kTile;
+    const size_t bytes = static_cast<size_t>(p->book.capacity()) * kTile;
     if (!g && !g.acquire_mapped(p->device, bytes)) {
         (void)fail(CEC_ENOMEM, "recovery pool: %zu bytes of staging for parity %d's residuals", bytes, parity_lid);
         return nullptr;
@@ -333,16 +260,14 @@ static Buf *pool_given_staging(cec_recovery_pool *p, int parity_lid) {
 }
 
 CEC_API uint8_t *cec_recovery_pool_parity_staging(cec_recovery_pool *p, int id, int parity_lid, size_t *len) {
-    cec_recovery_pool::Req *r = pool_req(p, id);
+    const poolbook::Req *r = pool_find(p, id);
     if (!r) {
         (void)fail(CEC_EINVAL, "cec_recovery_pool_parity_staging: request %d", id);
         return nullptr;
     }
     // only where add_residual would take one: another parity of a multi-loss request's mask
     // (given already or not) -- nothing is acquired for any other lid or request
-    poolbook::Req view = pool_book_req(p, id);
-    view.given = 0;
-    if (poolbook::check_residual(p->code.k, p->code.m, p->lid_self, view, parity_lid)) {
+    if (const poolbook::Refusal why = p->book.check_residual(id, parity_lid); why && why != poolbook::kTwice) {
         (void)fail(CEC_EINVAL, "cec_recovery_pool_parity_staging: request %d takes no residual of lid %d", id,
                    parity_lid);
         return nullptr;
@@ -363,7 +288,7 @@ static const char *const kResidualRefusal[] = {
 static int pool_give(cec_recovery_pool *p, const char *op, const int *ids, const int *lids,
                      const void *const *residuals, int n) {
     for (int i = 0; i < n; ++i) {
-        const cec_recovery_pool::Req &r = p->reqs[ids[i]];
+        const poolbook::Req &r = p->book.reqs[ids[i]];
         Buf *g = pool_given_staging(p, lids[i]);
         if (!g) return CEC_ENOMEM;
         const size_t off = static_cast<size_t>(r.slot) * kTile, len = static_cast<size_t>(r.nunits) * kTile;
@@ -384,10 +309,8 @@ static int pool_give(cec_recovery_pool *p, const char *op, const int *ids, const
             memcpy(dst, residuals[i], len);
         }
     }
-    for (int i = 0; i < n; ++i) {
-        p->reqs[ids[i]].given |= 1u << lids[i];
-        pool_enqueue(p, ids[i]);  // its last residual may make it ready: the next flush looks
-    }
+    // (a request's last residual may make it ready: the next flush looks)
+    for (int i = 0; i < n; ++i) p->book.note_residual(ids[i], lids[i]);
     return CEC_OK;
 }
 
@@ -398,8 +321,7 @@ CEC_API int cec_recovery_pool_add_residuals(cec_recovery_pool *p, const int *ids
     for (int i = 0; i < n; ++i)
         if (!residuals[i]) return fail(CEC_EINVAL, "cec_recovery_pool_add_residuals: residual %d is NULL", i);
     int bad = 0;
-    if (poolbook::Refusal why = poolbook::check_residuals(
-            p->code.k, p->code.m, p->lid_self, ids, parity_lids, n, [p](int id) { return pool_book_req(p, id); }, &bad))
+    if (poolbook::Refusal why = p->book.check_residuals(ids, parity_lids, n, &bad))
         return fail(CEC_EINVAL, "cec_recovery_pool_add_residuals: residual %d (request %d, parity %d): %s", bad,
                     ids[bad], parity_lids[bad], kResidualRefusal[why]);
     return pool_give(p, "cec_recovery_pool_add_residuals", ids, parity_lids, residuals, n);
@@ -407,23 +329,16 @@ CEC_API int cec_recovery_pool_add_residuals(cec_recovery_pool *p, const int *ids
 
 CEC_API int cec_recovery_pool_add_residual(cec_recovery_pool *p, int id, int parity_lid, const void *residual) {
     if (!p || !residual) return fail(CEC_EINVAL, "cec_recovery_pool_add_residual: bad args");
-    if (poolbook::Refusal why =
-            poolbook::check_residual(p->code.k, p->code.m, p->lid_self, pool_book_req(p, id), parity_lid))
+    if (poolbook::Refusal why = p->book.check_residual(id, parity_lid))
         return fail(CEC_EINVAL, "cec_recovery_pool_add_residual: request %d, parity %d: %s", id, parity_lid,
                     kResidualRefusal[why]);
     return pool_give(p, "cec_recovery_pool_add_residual", &id, &parity_lid, &residual, 1);
 }
 
-CEC_API int cec_recovery_pool_ready(const cec_recovery_pool *p, int id) {
-    return p && poolbook::ready(p->code.k, p->lid_self, pool_book_req(p, id)) ? 1 : 0;
-}
+CEC_API int cec_recovery_pool_ready(const cec_recovery_pool *p, int id) { return p && p->book.ready(id) ? 1 : 0; }
 
-// Fold every queued reply in one launch.  With `out` (k arenas by data lid), a request
-// that this flush completes and that is a single loss led by this parity is solved in
-// the same pass: out[lost][off] = inv * R'[slot], from the same inputs (exact in GF(2^8),
-// as cec_recovery_finish).  Returns the requests folded; *solved gets those solved.
 static int pool_out_host(cec_recovery_pool *p, int planes) {  // the _host solves' output planes, on first use
-    const size_t bytes = static_cast<size_t>(p->capacity) * kTile;
+    const size_t bytes = static_cast<size_t>(p->book.capacity()) * kTile;
     for (int x = 0; x < planes; ++x)
         if (!p->out[x] && !p->out[x].acquire_mapped(p->device, bytes))
             return fail(CEC_ENOMEM, "recovery pool: %zu bytes of host output (plane %d)", bytes, x);
@@ -450,14 +365,6 @@ struct FlushStreams {
     }
 };
 
-// The lost data lids of a mask, ascending (as C[] / data[] are ordered, memcached.c:7911-7922).
-static int pool_lost_lids(const cec_recovery_pool *p, uint32_t mask, int *lost) {
-    int n = 0;
-    for (int j = 0; j < p->code.k; ++j)
-        if (!(mask & (1u << j))) lost[n++] = j;
-    return n;
-}
-
 // One combination that rebuilds the n lost shards of `mask` from C[self] = sum_i a[i] *
 // (input i of c, i < n_self: R itself, or the inputs of a flush's R') and the given
 // residuals, which it adds as inputs from the slots given_slot(parity lid):
@@ -468,7 +375,7 @@ static int pool_solve_combo(const cec_recovery_pool *p, uint32_t mask, Combo &c,
                             GivenSlot given_slot, OutSlot out_slot, bool by_src) {
     Loss ls;
     if (int rc = Loss::of(p->code, mask, "recovery pool", &ls)) return rc;
-    const int self = ls.index_of_parity(p->lid_self);
+    const int self = ls.index_of_parity(p->book.self);
     if (self < 0) return fail(CEC_EINVAL, "recovery pool: mask 0x%x does not name this parity", mask);
     int in_given[CEC_MAX_M];
     for (int r = 0; r < ls.n; ++r)
@@ -493,45 +400,27 @@ static int pool_diff_staging(cec_recovery_pool *p, size_t len, const char *op) {
 static int pool_solve_run(cec_recovery_pool *p, int dev, std::vector<int> ids, uint8_t *const *out, bool to_host,
                           hipStream_t s);
 
-// to_host: the solves go to the host planes at the request's slots instead of out[lost].
-static int pool_flush(cec_recovery_pool *p, uint8_t *const *out, bool to_host, void *stream, int *solved) {
-    if (solved) *solved = 0;
-    if (p->queued_ids.empty()) return 0;
+static uint32_t pool_arenas(uint8_t *const *out, int k) {  // the data lids with an output arena, as the book's bit set
+    uint32_t have = 0;
+    for (int j = 0; j < k && out; ++j) have |= out[j] ? 1u << j : 0;
+    return have;
+}
+
+// Fold every queued reply in one launch.  With `out` (k arenas by data lid) or to_host (the
+// host planes at the request's slots instead of out[lost]), a request that this flush makes
+// ready is solved in the same pass, from the same inputs (exact in GF(2^8), as
+// cec_recovery_finish).  Returns the requests solved, or for a pass that solves none, folded.
+static int pool_flush(cec_recovery_pool *p, uint8_t *const *out, bool to_host, void *stream) {
+    const std::vector<int> &queued = p->book.queued_ids;
+    if (queued.empty()) return 0;
     int dev;
     if (int rc = current_device(&dev)) return rc;
     if (dev != p->device) return fail(CEC_EINVAL, "pool of device %d used on %d", p->device, dev);
     hipStream_t s = static_cast<hipStream_t>(stream);
     UseNote note_{p->uses, s};
     const int k = p->code.k;
-    // What the pass does with each queued request: fold its replies (kFold), fold and solve in
-    // the same launch (kFused: ready, at most three losses -- R' and the shards are the
-    // launch's four outputs), fold now and solve behind the launch (`later`: ready, four
-    // losses or more), or nothing (a residual came, and the request is not ready or the pass
-    // does not solve).
-    enum { kNothing, kFold, kFused };
-    std::vector<char> plan(p->queued_ids.size(), kNothing);
-    std::vector<int> later;
-    int planes = 0;
-    for (size_t x = 0; x < p->queued_ids.size(); ++x) {
-        const int id = p->queued_ids[x];
-        const cec_recovery_pool::Req &r = p->reqs[id];
-        if (r.queued || r.touch_pending) plan[x] = kFold;
-        if (!(out || to_host) || !cec_recovery_pool_ready(p, id)) continue;
-        int lost[CEC_MAX_K];
-        const int n = pool_lost_lids(p, r.mask, lost);
-        bool have_out = true;  // (a lost lid's arena not given: folded only, as ever)
-        for (int i = 0; i < n && !to_host; ++i) have_out &= out[lost[i]] != nullptr;
-        if (!have_out) continue;
-        if (n <= poolbook::kFusedLosses) {
-            plan[x] = kFused;
-            planes = std::max(planes, n);
-        } else {
-            later.push_back(id);
-        }
-    }
-    if (to_host) {
-        if (int rc = pool_out_host(p, planes)) return rc;
-    }
+    poolbook::Plan plan = p->book.plan_flush(out || to_host, to_host, pool_arenas(out, k));
+    if (int rc = pool_out_host(p, plan.planes)) return rc;  // (none unless to_host)
     const FlushStreams fs(p, out, to_host);
     const int engine = op_engine(false);
     if (p->tables.engine != engine) {  // the table's coefficient form is per engine
@@ -542,10 +431,10 @@ static int pool_flush(cec_recovery_pool *p, uint8_t *const *out, bool to_host, v
     std::vector<char> used;
     size_t nt = 0;
     int folded = 0;
-    for (size_t x = 0; x < p->queued_ids.size(); ++x) {
-        if (plan[x] == kNothing) continue;
-        const cec_recovery_pool::Req &r = p->reqs[p->queued_ids[x]];
-        const bool fused = plan[x] == kFused, folds = r.queued || r.touch_pending;
+    for (size_t x = 0; x < queued.size(); ++x) {
+        if (plan.action[x] == poolbook::kNothing) continue;
+        const poolbook::Req &r = p->book.reqs[queued[x]];
+        const bool fused = plan.action[x] == poolbook::kFused, folds = r.queued || r.touch_pending;
         const uint64_t key = poolbook::flush_key(r.queued, r.touch_pending, fused, r.mask, to_host);
         auto it = p->flush_pat.find(key);
         if (it == p->flush_pat.end()) {
@@ -555,7 +444,7 @@ static int pool_flush(cec_recovery_pool *p, uint8_t *const *out, bool to_host, v
             int a[kPatN] = {};
             a[r.touch_pending ? c.in(fs.at.parity()) : c.in(fs.at.residual(), true)] = 1;
             for (int j = 0; j < k; ++j)
-                if (r.queued & (1u << j)) a[c.in(fs.at.reply(j), true)] = p->code.at(p->lid_self, j);  // recovery.c:91-93
+                if (r.queued & (1u << j)) a[c.in(fs.at.reply(j), true)] = p->code.at(p->book.self, j);  // recovery.c:91-93
             const int n_self = c.n_in;  // (<= k - n + 1; the given residuals make it at most k)
             if (folds) {  // (a residual-only pass leaves R as it is)
                 Combo::Out &o = c.out(fs.at.residual(), kModeWrite, true);
@@ -575,7 +464,7 @@ static int pool_flush(cec_recovery_pool *p, uint8_t *const *out, bool to_host, v
         }
         used.resize(p->tables.pats.size(), 0);
         used[it->second] = 1;
-        if (nt + r.nunits > static_cast<size_t>(p->capacity))  // (cannot happen: the queue holds an id once)
+        if (nt + r.nunits > static_cast<size_t>(p->book.capacity()))  // (cannot happen: the queue holds an id once)
             return fail(CEC_EINVAL, "recovery pool: a flush of more units than the tile buffer; not launched");
         nt += append_tiles(p->tiles.get<Tile>() + nt, static_cast<uint64_t>(r.ub) * kTile,
                            static_cast<uint64_t>(r.slot) * kTile, static_cast<uint32_t>(r.nunits) * kTile,
@@ -595,56 +484,35 @@ static int pool_flush(cec_recovery_pool *p, uint8_t *const *out, bool to_host, v
         // tile buffer and staging reusable; rebuilt shards visible if out is host memory
         if (int rc = stream_wait(s, to_host || (out && any_host_memory(out, k)))) return rc;
     }
-    int n_solved = 0;
-    for (size_t x = 0; x < p->queued_ids.size(); ++x) {
-        cec_recovery_pool::Req &r = p->reqs[p->queued_ids[x]];
-        r.queued = 0;
-        r.touch_pending = false;
-        r.enqueued = false;
-        if (plan[x] == kFused) {
-            r.solved = true;
-            r.solved_host = to_host;
-            ++n_solved;
-        }
-    }
-    p->queued_ids.clear();
-    if (solved) *solved = n_solved;
+    const int n_solved = p->book.commit_flush(plan, to_host) + static_cast<int>(plan.later.size());
     // Four losses and more: R' is in HBM and the launch above is complete (the tile buffer is
     // free again), so the solve reads the new R as an explicit solve would -- the hazard of
     // cec_recovery_finish's R' (an output over an input of a split combination) does not arise.
-    if (!later.empty()) {
-        const int n_later = static_cast<int>(later.size());
-        if (int rc = pool_solve_run(p, dev, std::move(later), out, to_host, s)) return rc;
-        if (solved) *solved = n_solved + n_later;
-    }
-    return folded;
+    if (!plan.later.empty())
+        if (int rc = pool_solve_run(p, dev, std::move(plan.later), out, to_host, s)) return rc;
+    return out || to_host ? n_solved : folded;
 }
 
 CEC_API int cec_recovery_pool_flush(cec_recovery_pool *p, void *stream) {
     if (!p) return fail(CEC_EINVAL, "cec_recovery_pool_flush: pool is NULL");
-    return pool_flush(p, nullptr, false, stream, nullptr);
+    return pool_flush(p, nullptr, false, stream);
 }
 
 CEC_API int cec_recovery_pool_flush_solve(cec_recovery_pool *p, uint8_t *const *out, void *stream) {
     if (!p || !out) return fail(CEC_EINVAL, "cec_recovery_pool_flush_solve: bad args");
-    int solved = 0;
-    const int rc = pool_flush(p, out, false, stream, &solved);
-    return rc < 0 ? rc : solved;
+    return pool_flush(p, out, false, stream);
 }
 
 CEC_API int cec_recovery_pool_flush_solve_host(cec_recovery_pool *p, void *stream) {
     if (!p) return fail(CEC_EINVAL, "cec_recovery_pool_flush_solve_host: pool is NULL");
-    int solved = 0;
-    const int rc = pool_flush(p, nullptr, true, stream, &solved);
-    return rc < 0 ? rc : solved;
+    return pool_flush(p, nullptr, true, stream);
 }
 
 CEC_API const uint8_t *cec_recovery_pool_output_lost(const cec_recovery_pool *p, int id, int x, size_t *len) {
-    if (!p || id < 0 || id >= static_cast<int>(p->reqs.size()) || !p->reqs[id].used) return nullptr;
-    const cec_recovery_pool::Req &r = p->reqs[id];
-    if (!r.solved || !r.solved_host || x < 0 || x >= poolbook::n_lost(p->code.k, r.mask) || !p->out[x]) return nullptr;
-    if (len) *len = static_cast<size_t>(r.nunits) * kTile;
-    return p->out[x].get() + static_cast<size_t>(r.slot) * kTile;
+    const poolbook::Req *r = pool_find(p, id);
+    if (!r || !r->solved || !r->solved_host || x < 0 || x >= p->book.n_lost(r->mask) || !p->out[x]) return nullptr;
+    if (len) *len = static_cast<size_t>(r->nunits) * kTile;
+    return p->out[x].get() + static_cast<size_t>(r->slot) * kTile;
 }
 
 CEC_API const uint8_t *cec_recovery_pool_output(const cec_recovery_pool *p, int id, size_t *len) {
@@ -652,16 +520,11 @@ CEC_API const uint8_t *cec_recovery_pool_output(const cec_recovery_pool *p, int 
 }
 
 CEC_API int cec_recovery_pool_solved(const cec_recovery_pool *p, int id) {
-    if (!p || id < 0 || id >= static_cast<int>(p->reqs.size()) || !p->reqs[id].used) return 0;
-    return p->reqs[id].solved ? 1 : 0;
+    const poolbook::Req *r = pool_find(p, id);
+    return r && r->solved ? 1 : 0;
 }
 
-CEC_API int cec_recovery_pool_complete(const cec_recovery_pool *p, int id) {
-    if (!p || id < 0 || id >= static_cast<int>(p->reqs.size()) || !p->reqs[id].used) return 0;
-    const cec_recovery_pool::Req &r = p->reqs[id];
-    const uint32_t data = r.mask & ((1u << p->code.k) - 1);
-    return (r.contributed & data) == data ? 1 : 0;
-}
+CEC_API int cec_recovery_pool_complete(const cec_recovery_pool *p, int id) { return p && p->book.complete(id) ? 1 : 0; }
 
 CEC_API int cec_recovery_pool_fold_update(cec_recovery_pool *p, int peer, uint64_t addr, const void *diff,
                                           uint32_t len, void *stream) {
@@ -674,23 +537,13 @@ CEC_API int cec_recovery_pool_fold_update(cec_recovery_pool *p, int peer, uint64
     hipStream_t s = static_cast<hipStream_t>(stream);
     UseNote note_{p->uses, s};
     if (int rc = cec_recovery_pool_flush(p, stream); rc < 0) return rc;
-    // tiles: the pieces of [addr, addr+len) inside touched requests peer has not fed,
-    // slot-addressed (R) and diff-addressed (src_off); at most one tile per unit, so
-    // they fit the pool's tile buffer.  No test of the mask: recovery.c:116-120 folds a
-    // lost lid's diffs too (a substitute forwards them under that lid, memcached.c:7700,
-    // :7758), and they are what keeps R equal to the lost shard's live bytes.
+    // tiles: the update's pieces, slot-addressed (R) and diff-addressed (src_off); at most
+    // one tile per unit, so they fit the pool's tile buffer
+    std::vector<poolbook::Piece> pieces;
+    const int units = p->book.pieces(p->book.touched_spans(), addr, len, peer, 0, pieces);
     size_t nt = 0;
-    int units = 0;
-    for (cec_recovery_pool::Req &r : p->reqs) {
-        if (!r.used || !r.touched || (r.contributed & (1u << peer))) continue;
-        const uint64_t base = static_cast<uint64_t>(r.ub) * kTile, end = base + static_cast<uint64_t>(r.nunits) * kTile;
-        const uint64_t lo = std::max(addr, base), hi = std::min(addr + len, end);
-        if (lo >= hi) continue;
-        r.solved = r.solved_host = false;  // (a lost lid's diff after the solve: R moved on)
-        nt += append_tiles(p->tiles.get<Tile>() + nt, static_cast<uint64_t>(r.slot) * kTile + (lo - base), lo - addr,
-                           static_cast<uint32_t>(hi - lo), 0);
-        units += static_cast<int>((hi - 1) / kTile - lo / kTile + 1);
-    }
+    for (const poolbook::Piece &pc : pieces)  // (a lost lid's diff after the solve: R moved on)
+        nt += append_tiles(p->tiles.get<Tile>() + nt, pc.r_off, pc.d_off, pc.len, 0);
     if (nt == 0) return 0;
     const uint8_t *d = static_cast<const uint8_t *>(device_view_of(diff));
     if (!d) {  // pageable diff: through the pool's mapped pinned staging (zero-copy)
@@ -698,7 +551,7 @@ CEC_API int cec_recovery_pool_fold_update(cec_recovery_pool *p, int peer, uint64
         memcpy(p->diff.get(), diff, len);
         d = p->diff.alias();
     }
-    const Fold f = fold(p->code, p->lid_self, d, p->residual.get(), peer);  // recovery.c:123
+    const Fold f = fold(p->code, p->book.self, d, p->residual.get(), peer);  // recovery.c:123
     if (int rc = run_combos(dev, f.st, f.combos, TileSource::window(p->tiles.alias<Tile>(), p->tiles.get<Tile>(), nt), s))
         return rc;
     if (int rc = stream_wait(s, false)) return rc;  // (the residual is in HBM)
@@ -727,58 +580,23 @@ CEC_API int cec_recovery_pool_fold_updates(cec_recovery_pool *p, const cec_host_
     hipStream_t s = static_cast<hipStream_t>(stream);
     UseNote note_{p->uses, s};
     if (int rc = cec_recovery_pool_flush(p, stream); rc < 0) return rc;
-    // the touched requests by arena range, with the running max of their ends (requests
-    // may overlap in the pool's API; the server's do not)
-    struct Span {
-        uint64_t base, end;
-        int id;
-    };
-    std::vector<Span> spans;
-    for (int id = 0; id < static_cast<int>(p->reqs.size()); ++id) {
-        const cec_recovery_pool::Req &r = p->reqs[id];
-        if (!r.used || !r.touched) continue;
-        const uint64_t base = static_cast<uint64_t>(r.ub) * kTile;
-        spans.push_back({base, base + static_cast<uint64_t>(r.nunits) * kTile, id});
-    }
-    if (spans.empty()) return 0;
-    std::sort(spans.begin(), spans.end(), [](const Span &a, const Span &b) { return a.base < b.base; });
-    std::vector<uint64_t> max_end(spans.size());
-    for (size_t i = 0; i < spans.size(); ++i) max_end[i] = std::max(spans[i].end, i ? max_end[i - 1] : 0);
-    struct Piece {
-        uint64_t r_off;   // in R
-        uint64_t d_off;   // in the update's buffer
-        uint32_t len;
-        int upd;
-    };
-    std::vector<Piece> pieces;
-    size_t staged = 0;
+    const std::vector<poolbook::Span> spans = p->book.touched_spans();
+    std::vector<poolbook::Piece> pieces;
     int total_units = 0;
-    for (int i = 0; i < n; ++i) {
-        const uint64_t a = u[i].addr, b = u[i].addr + u[i].len;
-        const int peer = static_cast<int>(u[i].src_lid);
-        size_t hi_idx = std::upper_bound(spans.begin(), spans.end(), b,
-                                         [](uint64_t v, const Span &x) { return v <= x.base; }) - spans.begin();
-        for (size_t x = hi_idx; x-- > 0 && max_end[x] > a;) {
-            cec_recovery_pool::Req &r = p->reqs[spans[x].id];
-            if (r.contributed & (1u << peer)) continue;  // recovery.c:116-120 (no mask test, as fold_update)
-            const uint64_t lo = std::max(a, spans[x].base), hi = std::min(b, spans[x].end);
-            if (lo >= hi) continue;
-            pieces.push_back({static_cast<uint64_t>(r.slot) * kTile + (lo - spans[x].base), lo - a,
-                              static_cast<uint32_t>(hi - lo), i});
-            staged += hi - lo;
-            const int nu = static_cast<int>((hi - 1) / kTile - lo / kTile + 1);
-            total_units += nu;
-            if (units) units[i] += nu;
-            r.solved = r.solved_host = false;
-        }
+    for (int i = 0; i < n && !spans.empty(); ++i) {
+        const int nu = p->book.pieces(spans, u[i].addr, u[i].len, static_cast<int>(u[i].src_lid), i, pieces);
+        total_units += nu;
+        if (units) units[i] = nu;
     }
+    size_t staged = 0;
+    for (const poolbook::Piece &pc : pieces) staged += pc.len;
     if (pieces.empty()) return 0;
     if (int rc = pool_diff_staging(p, staged, "cec_recovery_pool_fold_updates")) return rc;
     // tiles (one per unit piece: R offsets are unit-aligned per slot), packed pieces
     std::vector<Tile> tiles;
     tiles.reserve(pieces.size() + staged / kTile + 1);
     size_t so = 0;
-    for (const Piece &pc : pieces) {
+    for (const poolbook::Piece &pc : pieces) {
         memcpy(p->diff.get() + so, static_cast<const uint8_t *>(u[pc.upd].buf) + pc.d_off, pc.len);
         Tile tmp[33];
         for (uint32_t o = 0; o < pc.len;) {  // <= 32 units per step: <= 33 tiles (append_tiles' split)
@@ -803,7 +621,7 @@ CEC_API int cec_recovery_pool_fold_updates(cec_recovery_pool *p, const cec_host_
     for (size_t t = 0; t < nt; ++t) order[at[wave_of[t]]++] = t;
     // the tile buffer: the pool's own, or for a window wider than it, a cached one
     Buf wide;
-    const Buf &tb = nt <= static_cast<size_t>(p->capacity) ? p->tiles : wide;
+    const Buf &tb = nt <= static_cast<size_t>(p->book.capacity()) ? p->tiles : wide;
     if (&tb == &wide && !wide.acquire_mapped(dev, nt * sizeof(Tile)))
         return fail(CEC_ENOMEM, "cec_recovery_pool_fold_updates: %zu tiles", nt);
     WaveTiles wt(tb.get<Tile>());
@@ -812,9 +630,9 @@ CEC_API int cec_recovery_pool_fold_updates(cec_recovery_pool *p, const cec_host_
         wt.add(tiles[t].off, tiles[t].src_off, tiles[t].len, tiles[t].pattern);  // (one tile each, as cut above)
     }
     // the packed diff pieces into R; pattern index = the update's data lid (recovery.c:123)
-    const Fold f = fold(p->code, p->lid_self, p->diff.alias(), p->residual.get());
+    const Fold f = fold(p->code, p->book.self, p->diff.alias(), p->residual.get());
     std::vector<char> used(p->code.k, 0);
-    for (const Piece &pc : pieces) used[u[pc.upd].src_lid] = 1;
+    for (const poolbook::Piece &pc : pieces) used[u[pc.upd].src_lid] = 1;
     // an earlier wave may still read the diff staging and the tiles (the pool's own or `wide`,
     // which goes back to the cache after the guard), which the next call overwrites from the host
     InFlight guard(s);
@@ -837,12 +655,12 @@ CEC_API int cec_recovery_pool_fold_updates(cec_recovery_pool *p, const cec_host_
 static int pool_solve_run(cec_recovery_pool *p, int dev, std::vector<int> ids, uint8_t *const *out, bool to_host,
                           hipStream_t s) {
     const int k = p->code.k;
-    auto losses = [&](int id) { return poolbook::n_lost(k, p->reqs[id].mask); };
+    const poolbook::Book &book = p->book;
+    auto losses = [&](int id) { return book.n_lost(book.reqs[id].mask); };
+    auto only_lost = [&](int id) { return __builtin_ctz(book.lost_lids(book.reqs[id].mask)); };  // of a single loss
     std::stable_sort(ids.begin(), ids.end(), [&](int a, int b) { return losses(a) > losses(b); });
     const int n_max = losses(ids.front());
-    if (to_host) {
-        if (int rc = pool_out_host(p, n_max)) return rc;
-    }
+    if (int rc = pool_out_host(p, to_host ? n_max : 0)) return rc;
     Streams st;
     const int s_residual = st.add(p->residual.get());
     int s_plane[CEC_MAX_M], s_given[CEC_MAX_M], s_arena[CEC_MAX_K];
@@ -856,20 +674,18 @@ static int pool_solve_run(cec_recovery_pool *p, int dev, std::vector<int> ids, u
         const int in_r = c.in(s_residual, true);  // R, slot-addressed
         // plane 0, slot-addressed; or the lost lid's arena, arena offset
         Combo::Out &o = to_host ? c.out(s_plane[0], kModeWrite, true) : c.out(s_arena[x], kModeWrite);
-        const int cx = p->code.at(p->lid_self, x);
+        const int cx = p->code.at(p->book.self, x);
         o.coef[in_r] = cx ? gf_inv(cx) : 0;  // memcached.c:7907-7922, n_lost = 1
     }
     std::map<uint32_t, int> combo_of;  // multi-loss mask -> its combination
     size_t nt = 0;
     std::vector<size_t> tiles_upto(poolbook::solve_launches(n_max), 0);  // launch g's prefix of the tiles
     for (int id : ids) {
-        const cec_recovery_pool::Req &r = p->reqs[id];
+        const poolbook::Req &r = book.reqs[id];
         const int n = losses(id);
         int pattern;
         if (n == 1) {
-            int lost[CEC_MAX_K];
-            (void)pool_lost_lids(p, r.mask, lost);
-            pattern = lost[0];
+            pattern = only_lost(id);
         } else {
             auto it = combo_of.find(r.mask);
             if (it == combo_of.end()) {
@@ -893,7 +709,7 @@ static int pool_solve_run(cec_recovery_pool *p, int dev, std::vector<int> ids, u
             }
             pattern = it->second;
         }
-        if (nt + r.nunits > static_cast<size_t>(p->capacity))  // (cannot happen once ids are distinct)
+        if (nt + r.nunits > static_cast<size_t>(p->book.capacity()))  // (cannot happen once ids are distinct)
             return fail(CEC_EINVAL, "cec_recovery_pool_solve: more units than the tile buffer");
         nt += append_tiles(p->tiles.get<Tile>() + nt, static_cast<uint64_t>(r.ub) * kTile,
                            static_cast<uint64_t>(r.slot) * kTile, static_cast<uint32_t>(r.nunits) * kTile,
@@ -905,13 +721,10 @@ static int pool_solve_run(cec_recovery_pool *p, int dev, std::vector<int> ids, u
         // the combinations launch g's tiles name: those listed that have an output past 4g
         std::vector<char> used(combos.size(), 0);
         for (int id : ids) {
-            const cec_recovery_pool::Req &r = p->reqs[id];
             if (losses(id) == 1) {
-                int lost[CEC_MAX_K];
-                (void)pool_lost_lids(p, r.mask, lost);
-                used[lost[0]] = g == 0;
+                used[only_lost(id)] = g == 0;
             } else if (losses(id) > static_cast<int>(g) * kPatL) {
-                used[combo_of[r.mask]] = 1;
+                used[combo_of[book.reqs[id].mask]] = 1;
             }
         }
         std::vector<Pattern> pats;
@@ -923,10 +736,7 @@ static int pool_solve_run(cec_recovery_pool *p, int dev, std::vector<int> ids, u
             return rc;
     }
     if (int rc = stream_wait(s, to_host || any_host_memory(out, k))) return rc;
-    for (int id : ids) {
-        p->reqs[id].solved = true;
-        p->reqs[id].solved_host = to_host;
-    }
+    p->book.mark_solved(ids, to_host);
     return CEC_OK;
 }
 
@@ -941,20 +751,20 @@ static int pool_solve(cec_recovery_pool *p, const int *ids, int n, uint8_t *cons
     if (int rc = cec_recovery_pool_flush(p, stream); rc < 0) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     UseNote note_{p->uses, s};
-    std::vector<char> listed(p->reqs.size(), 0);
-    for (int x = 0; x < n; ++x) {
-        cec_recovery_pool::Req *r = pool_req(p, ids[x]);
-        if (!r || !cec_recovery_pool_complete(p, ids[x]))
-            return fail(CEC_EINVAL, "cec_recovery_pool_solve: request %d missing or incomplete", ids[x]);
-        if (listed[ids[x]]++) return fail(CEC_EINVAL, "cec_recovery_pool_solve: request %d listed twice", ids[x]);
-        if (!cec_recovery_pool_ready(p, ids[x]))
-            return fail(CEC_EINVAL, "cec_recovery_pool_solve: request %d loses %d shards and not every other "
-                                    "participating parity's residual has been given (cec_recovery_pool_add_residual)",
-                        ids[x], poolbook::n_lost(p->code.k, r->mask));
-        int lost[CEC_MAX_K];
-        const int nl = pool_lost_lids(p, r->mask, lost);
-        for (int i = 0; i < nl && !to_host; ++i)
-            if (!out[lost[i]]) return fail(CEC_EINVAL, "cec_recovery_pool_solve: out[%d] is NULL", lost[i]);
+    int x = 0;
+    const uint32_t arenas = pool_arenas(out, p->code.k);
+    switch (p->book.check_solve(ids, n, to_host, arenas, &x)) {
+    case poolbook::kAccepted: break;
+    case poolbook::kIncomplete:
+        return fail(CEC_EINVAL, "cec_recovery_pool_solve: request %d missing or incomplete", ids[x]);
+    case poolbook::kListedTwice: return fail(CEC_EINVAL, "cec_recovery_pool_solve: request %d listed twice", ids[x]);
+    case poolbook::kNotReady:
+        return fail(CEC_EINVAL, "cec_recovery_pool_solve: request %d loses %d shards and not every other "
+                                "participating parity's residual has been given (cec_recovery_pool_add_residual)",
+                    ids[x], p->book.n_lost(p->book.reqs[ids[x]].mask));
+    default:
+        return fail(CEC_EINVAL, "cec_recovery_pool_solve: out[%d] is NULL",
+                    __builtin_ctz(p->book.lost_lids(p->book.reqs[ids[x]].mask) & ~arenas));
     }
     return pool_solve_run(p, dev, std::vector<int>(ids, ids + n), out, to_host, s);
 }
@@ -969,7 +779,7 @@ CEC_API int cec_recovery_pool_solve_host(cec_recovery_pool *p, const int *ids, i
 }
 
 CEC_API int cec_recovery_pool_residual(cec_recovery_pool *p, int id, void *dst, void *stream) {
-    cec_recovery_pool::Req *r = pool_req(p, id);
+    const poolbook::Req *r = pool_find(p, id);
     if (!r || !dst) return fail(CEC_EINVAL, "cec_recovery_pool_residual: request %d / dst", id);
     if (int rc = cec_recovery_pool_flush(p, stream); rc < 0) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -981,24 +791,12 @@ CEC_API int cec_recovery_pool_residual(cec_recovery_pool *p, int id, void *dst, 
 }
 
 CEC_API int cec_recovery_pool_end(cec_recovery_pool *p, int id) {
-    cec_recovery_pool::Req *r = pool_req(p, id);
+    const poolbook::Req *r = pool_find(p, id);
     if (!r) return fail(CEC_EINVAL, "cec_recovery_pool_end: request %d", id);
-    if (r->queued) {  // a reply still queued: fold it first, it may share a tile list
-        if (int rc = cec_recovery_pool_flush(p, nullptr); rc < 0) return rc;
-    }
-    // Still in the queue with nothing to fold (a residual came since the last flush): taken
-    // out, or the id -- reused by the next begin, which clears `enqueued` -- would be queued
-    // a second time and its tiles appended twice.
-    poolbook::dequeue(p->queued_ids, r->enqueued, id);
-    for (int s = r->slot; s < r->slot + r->nunits; ++s) p->slot_owner[s] = -1;
-    r->used = false;
-    p->free_ids.push_back(id);
+    // a reply still queued: fold it first, it may share a tile list
+    if (int rc = r->queued ? cec_recovery_pool_flush(p, nullptr) : 0; rc < 0) return rc;
+    p->book.end(id);  // (also out of the queue, where a residual since the last flush left it)
     return CEC_OK;
 }
 
-CEC_API int cec_recovery_pool_active(const cec_recovery_pool *p) {
-    if (!p) return 0;
-    int n = 0;
-    for (const cec_recovery_pool::Req &r : p->reqs) n += r.used;
-    return n;
-}
+CEC_API int cec_recovery_pool_active(const cec_recovery_pool *p) { return p ? p->book.active() : 0; }

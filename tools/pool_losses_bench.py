@@ -22,10 +22,11 @@ into the pool's stagings before the clock starts), begin / end are outside the c
 
 Every pass's rebuilt bytes are compared with the data.
 
---ab PARENT_LIB: the check that the single-loss pass kept its time.  Child processes of this
-tool with --single-only, alternating between this build and PARENT_LIB (CEC_LIB_PATH), each
-under its own time limit; reported per build: the median of the children's medians and their
-range, the run-to-run spread the comparison is read against.
+--ab PARENT_LIB: the check that the pooled and the single-loss pass kept their time.  Child
+processes of this tool with --pool-only (those two passes alone), alternating between this
+build and PARENT_LIB (CEC_LIB_PATH), each under its own time limit; reported per pass and
+build: the median of the children's medians and their range, the run-to-run spread the
+comparison is read against (single_loss_ab, pooled_ab).
 
 One JSON line.
 
@@ -68,24 +69,34 @@ def pcie_raw(torch, nbytes=256 << 20, reps=4):
     return rates[0], rates[1]
 
 
-def ab_single_loss(parent_lib: str, rounds: int, iters: int, limit_s: int) -> dict:
-    """Alternating child processes: this build, the parent build, ... each --single-only."""
-    meds = {"this": [], "parent": []}
+AB_PASSES = ("single_loss", "pooled")
+
+
+def ab_pool_passes(parent_lib: str, rounds: int, iters: int, limit_s: int) -> dict:
+    """Alternating child processes: this build, the parent build, ... each --pool-only."""
+    meds = {name: {"this": [], "parent": []} for name in AB_PASSES}
     for _ in range(rounds):
         for which in ("this", "parent"):
             env = dict(os.environ)
             env.pop("CEC_LIB_PATH", None)
             if which == "parent":
                 env["CEC_LIB_PATH"] = os.path.abspath(parent_lib)
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--single-only", "--iters", str(iters)],
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--pool-only", "--iters", str(iters)],
                                env=env, capture_output=True, text=True, timeout=limit_s, check=True)
-            meds[which].append(json.loads(r.stdout.strip().splitlines()[-1])["single_loss"]["median_us"])
-    out = {w: {"median_of_medians_us": round(statistics.median(v), 2), "min_us": min(v), "max_us": max(v),
-               "children": v} for w, v in meds.items()}
-    out["this_minus_parent_us"] = round(out["this"]["median_of_medians_us"] - out["parent"]["median_of_medians_us"], 2)
-    out["run_to_run_spread_us"] = round(max(max(v) - min(v) for v in meds.values()), 2)
-    out["within_spread"] = abs(out["this_minus_parent_us"]) <= out["run_to_run_spread_us"]
-    return out
+            line = json.loads(r.stdout.strip().splitlines()[-1])
+            for name in AB_PASSES:
+                meds[name][which].append(line[name]["median_us"])
+    res = {}
+    for name in AB_PASSES:
+        out = {w: {"median_of_medians_us": round(statistics.median(v), 2), "min_us": min(v), "max_us": max(v),
+                   "children": v} for w, v in meds[name].items()}
+        out["this_minus_parent_us"] = round(out["this"]["median_of_medians_us"] - out["parent"]["median_of_medians_us"], 2)
+        out["run_to_run_spread_us"] = round(max(max(v) - min(v) for v in meds[name].values()), 2)
+        out["within_spread"] = abs(out["this_minus_parent_us"]) <= out["run_to_run_spread_us"]
+        # the merge criterion: this build's median inside the parent's own min-max
+        out["this_within_parent_range"] = out["parent"]["min_us"] <= out["this"]["median_of_medians_us"] <= out["parent"]["max_us"]
+        res[name + "_ab"] = out
+    return res
 
 
 def main() -> None:
@@ -93,6 +104,7 @@ def main() -> None:
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--single-only", action="store_true")
+    ap.add_argument("--pool-only", action="store_true", help="the pooled and the single-loss pass alone")
     ap.add_argument("--ab", metavar="PARENT_LIB")
     ap.add_argument("--ab-rounds", type=int, default=3)
     ap.add_argument("--ab-limit", type=int, default=120, help="seconds per child process")
@@ -202,8 +214,9 @@ def main() -> None:
             end(rids)
             return t
 
-        passes = {"single_loss": single_loss}
-        if not args.single_only:
+        pool_only = args.single_only or args.pool_only
+        passes = {"pooled": pooled, "single_loss": single_loss} if args.pool_only else {"single_loss": single_loss}
+        if not pool_only:
             from oracle import pyoracle
 
             p0u = [parity[0][u * U:(u + 1) * U].copy() for u in range(NREQ)]
@@ -245,20 +258,20 @@ def main() -> None:
                 us[name].append(fn())
         for name in passes:
             out[name] = stats(us[name])
-        if not args.single_only:
+        if not pool_only:
             med = {name: out[name]["median_us"] for name in passes}
             out["per_request_over_pooled_median"] = round(med["per_request"] / med["pooled"], 2)
             out["reference_per_request_over_pooled_median"] = round(med["reference_per_request"] / med["pooled"], 2)
             out["reference_one_range_over_pooled_median"] = round(med["reference_one_range"] / med["pooled"], 2)
             out["pooled_over_single_loss_median"] = round(med["pooled"] / med["single_loss"], 2)
-    if not args.single_only:
+    if not (args.single_only or args.pool_only):
         h2d, d2h = pcie_raw(torch)
         up, down = 2 * NREQ * U, 2 * NREQ * U  # replies + residuals read in place; two planes written
         floor = max(up / (h2d * 1e9), down / (d2h * 1e9)) * 1e6
         out["pcie_floor"] = {"h2d_bytes": up, "d2h_bytes": down, "GBps_raw": {"h2d": round(h2d, 1), "d2h": round(d2h, 1)},
                              "floor_us": round(floor, 2), "floor_over_pooled": round(floor / out["pooled"]["median_us"], 3)}
     if args.ab:
-        out["single_loss_ab"] = ab_single_loss(args.ab, args.ab_rounds, args.iters, args.ab_limit)
+        out.update(ab_pool_passes(args.ab, args.ab_rounds, args.iters, args.ab_limit))
     print(json.dumps(out))
 
 
