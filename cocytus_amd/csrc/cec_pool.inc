@@ -39,6 +39,13 @@
 //             reply or its last residual) solves it in its own launch up to three losses
 //             (R' and the shards are the launch's four outputs); past three the solve's
 //             launches follow the flush's in the same call and read the new R from HBM.
+//   no data   with k <= m a mask may name parities only.  No reply comes, so begin queues the
+//             request's first touch itself: the next flush writes R[slot] = P[off] (the pattern
+//             of no queued reply with the first touch, the parity its only input) and, if it
+//             solves and the other residuals are in, the k shards in the same launch (k <= 3)
+//             or behind it.  solve, residual and fold_update(s) flush first, so none reads the
+//             slots before that; an explicit solve that still has a first touch to make is
+//             that one flush launch ahead of its ceil(n / 4).
 //   updates   fold_update flushes first, so a queued reply is folded exactly when the
 //             reference would have folded it (before the next parity change), then
 //             R ^= c * diff where the request is touched and the peer has not contributed
@@ -469,7 +476,7 @@ static int pool_flush(cec_recovery_pool *p, uint8_t *const *out, bool to_host, v
         nt += append_tiles(p->tiles.get<Tile>() + nt, static_cast<uint64_t>(r.ub) * kTile,
                            static_cast<uint64_t>(r.slot) * kTile, static_cast<uint32_t>(r.nunits) * kTile,
                            static_cast<uint32_t>(it->second));
-        folded += folds;  // (a request only solved by this pass is not counted as folded)
+        folded += r.queued != 0;  // (not one only solved by this pass, nor a first touch without a reply)
     }
     if (nt) {
         used.resize(p->tables.pats.size(), 0);

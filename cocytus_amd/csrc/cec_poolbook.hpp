@@ -74,9 +74,10 @@ inline int repeated_pair(const int *a, const int *b, int n) {
     return -1;
 }
 
-// What a flush does with queued_ids[x]: fold its replies (kFold), fold and solve in the same
-// launch (kFused: ready, at most kFusedLosses), or nothing (a residual came, and the request is
-// not ready or the pass does not solve).  `later`: ready with more losses, solved behind the
+// What a flush does with queued_ids[x]: fold its replies, or make the first touch of a request
+// whose mask names no data lid (kFold), fold and solve in the same launch (kFused: ready, at
+// most kFusedLosses), or nothing (a residual came, and the request is not ready or the pass
+// does not solve).  `later`: ready with more losses, solved behind the
 // launch.  `planes`: the host output planes a to_host pass writes.
 enum Action : char { kNothing, kFold, kFused };
 struct Plan {
@@ -104,7 +105,8 @@ struct Book {
     int cursor = 0;               // next-fit start: O(1) amortised begin for unit-sized requests
     // The ids with something for the next flush, each at most once (Req::enqueued).  A flush
     // clears queue and marks; a request that ends while marked is taken out, so an id reused
-    // by the next begin -- which starts unmarked -- cannot enter twice.
+    // by the next begin -- which starts unmarked, or enters once itself (a mask without data
+    // lids) -- cannot enter twice.
     std::vector<int> queued_ids;
 
     Book() = default;
@@ -125,9 +127,13 @@ struct Book {
     }
     // ... and every other participating parity's residual given.  A single loss needs none:
     // ready == complete.
-    // OPEN: with k <= m a mask may name no data lid.  Such a request is complete at once and
-    // never touched, so once its residuals are given it is `ready && !touched`, and the flush
-    // plan and the solve check below let a solve read an R that never received P.
+    // With k <= m a mask may name no data lid: k parities rebuild all k shards.  Such a request
+    // is complete from the start (ready at once for k = 1), and its residual is R = P[range],
+    // the first-touch copy of recovery.c:79-82 with no fold behind it.  No reply will ever
+    // bring that copy about, so begin queues it: the next flush of any kind makes it (and
+    // solves in the same launch, if it solves and the request is ready), and every reader of R
+    // -- solve, residual, the pieces of an update -- flushes first.  Until then R[slot] holds
+    // what the slots' previous owner left, and check_solve refuses the request.
     bool ready(int id) const {
         const Req *r = find(id);
         return complete(id) && (r->given & needed(k, self, r->mask)) == needed(k, self, r->mask);
@@ -162,10 +168,15 @@ struct Book {
         free_ids.pop_back();
         reqs[id] = Req{true, mask, unit_begin, n, slot};
         std::fill_n(slot_owner.begin() + slot, n, id);
+        if (!data_lids(k, mask)) {  // no reply to wait for: the first touch goes into the next flush (ready, above)
+            reqs[id].touched = reqs[id].touch_pending = true;
+            enqueue(id);
+        }
         return id;
     }
-    // Still in the queue with nothing to fold (a residual came since the last flush): taken
-    // out.  (A reply still queued -- find(id)->queued -- is the caller's to flush first.)
+    // Still in the queue with nothing to fold (a residual came since the last flush, or the
+    // first touch of a mask without data lids is still to be made): taken out.  (A reply still
+    // queued -- find(id)->queued -- is the caller's to flush first.)
     void end(int id) {
         Req &r = reqs[id];
         if (r.enqueued) queued_ids.erase(std::remove(queued_ids.begin(), queued_ids.end(), id), queued_ids.end());
@@ -227,7 +238,7 @@ struct Book {
             const int id = queued_ids[x];
             const Req &r = reqs[id];
             if (r.queued || r.touch_pending) pl.action[x] = kFold;
-            if (!solves || !ready(id) || (!to_host && (lost_lids(r.mask) & ~arenas))) continue;  // (OPEN, above)
+            if (!solves || !ready(id) || (!to_host && (lost_lids(r.mask) & ~arenas))) continue;
             if (const int n = n_lost(r.mask); n > kFusedLosses) {
                 pl.later.push_back(id);
             } else {
@@ -249,12 +260,18 @@ struct Book {
         queued_ids.clear();
         return n_solved;
     }
-    // A solve list: live and complete, listed once, ready (OPEN, above), outputs there; *bad = the refused entry.
+    // R[slot] holds the request's residual: touched, and the first touch flushed.
+    bool holds_residual(int id) const {
+        const Req *r = find(id);
+        return r && r->touched && !r->touch_pending;
+    }
+    // A solve list: live and complete with R in place (the caller flushes first, so a queued
+    // first touch is made by then), listed once, ready, outputs there; *bad = the refused entry.
     Refusal check_solve(const int *ids, int n, bool to_host, uint32_t arenas, int *bad) const {
         std::vector<char> listed(reqs.size(), 0);
         for (*bad = 0; *bad < n; ++*bad) {
             const int id = ids[*bad];
-            if (!complete(id)) return kIncomplete;
+            if (!complete(id) || !holds_residual(id)) return kIncomplete;
             if (listed[id]++) return kListedTwice;
             if (!ready(id)) return kNotReady;
             if (!to_host && (lost_lids(reqs[id].mask) & ~arenas)) return kNoOutput;

@@ -9,6 +9,7 @@
 //   add_peer (recovery_recover_units, recovery.c:61-96): first peer
 //       R = P[range] ^ c*D   (first-touch copy of the parity units fused in),
 //     later peers R ^= c*D, c = M[self][peer];
+//     a mask that names no data lid (k <= m) has no peer: create makes R = P[range] itself;
 //   fold_update (recovery_try_update_unit, recovery.c:99-131): R[piece] ^= c*diff
 //     while the range is touched and the peer has not contributed;
 //   solve (complete_recovery_bottom_half, memcached.c:7842-7922): out = inv * C.
@@ -118,6 +119,21 @@ CEC_API int cec_recovery_release_stream(cec_recovery *r, void *stream) {
     return CEC_OK;
 }
 
+// A mask that names no data lid (k <= m: k parities rebuild all k shards) has no peer whose
+// reply would bring the first touch about: R = P[range] (recovery.c:79-82, no fold behind it)
+// in one launch on s, complete on return.  From then on the session is touched, so every
+// later diff is folded into R as into any touched range.
+static int recovery_touch_alone(cec_recovery *r, hipStream_t s) {
+    UseNote note_{r->uses, s};
+    Streams st;
+    const int s_parity = st.add(r->parity), s_residual = st.add(r->residual);
+    if (int rc = run_combos_region(r->device, st, {multiply_combo(1, false, s_parity, s_residual)}, r->nbuf, s))
+        return rc;
+    if (int rc = stream_wait(s, false)) return rc;  // (the residual is in HBM)
+    r->touched = true;
+    return CEC_OK;
+}
+
 CEC_API int cec_recovery_create(cec_recovery **out, int k, int m, const int *matrix, int lid_self,
                                 uint32_t mask, int unit_begin, int unit_end,
                                 const uint8_t *parity_arena, void *stream) {
@@ -130,7 +146,6 @@ CEC_API int cec_recovery_create(cec_recovery **out, int k, int m, const int *mat
                     lid_self, mask, unit_begin, unit_end);
     int dev;
     if (int r = current_device(&dev)) return r;
-    (void)stream;
     cec_recovery *s = new (std::nothrow) cec_recovery;
     if (!s) return fail(CEC_ENOMEM, "cec_recovery_create: host allocation");
     s->device = dev;
@@ -153,6 +168,11 @@ CEC_API int cec_recovery_create(cec_recovery **out, int k, int m, const int *mat
         cec_recovery_destroy(s);
         return rc;
     }
+    if (!(mask & ((1u << k) - 1)))
+        if (int rc = recovery_touch_alone(s, static_cast<hipStream_t>(stream))) {
+            cec_recovery_destroy(s);
+            return rc;
+        }
     *out = s;
     return CEC_OK;
 }

@@ -326,7 +326,28 @@ int cec_region_multiply_batch_stats(cec_batch_stats *out);
  * pinned or pageable) are complete on return and the caller may reuse its buffers.
  * destroy waits only for the streams the session's calls used; work the CALLER queued
  * on cec_recovery_residual(r) (e.g. shipping it with cec_copy on another stream) must
- * be complete before destroy, since the residual's memory is then reused. */
+ * be complete before destroy, since the residual's memory is then reused.
+ *
+ * A MASK THAT NAMES NO DATA LID (k <= m: k parities rebuild all k shards).  No peer replies,
+ * so such a request -- a session or a pool request -- is complete from the start and holds the
+ * residual R = P[range] from the start: the live parity bytes (the first-touch copy of
+ * recovery.c:79-82 with no fold behind it), with every update folded that the parity arena
+ * has also received.  It is ready once the other n - 1 parities' residuals are given; for
+ * n = 1, which is k = 1, at once.  The reference never completes such a request
+ * (check_recovery_1st_completeness runs only when a reply arrives), so there is no behaviour
+ * of its to match; the bytes are those of its own arithmetic over the parities.
+ *   session: cec_recovery_create makes the copy, ONE launch on its stream, complete on
+ *     return; cec_recovery_residual holds P's bytes from then on, cec_recovery_fold_update
+ *     folds every later diff of any data lid, cec_recovery_solve rebuilds all k shards in
+ *     ceil(k / 4) launches.  cec_recovery_finish takes a data peer of the mask: CEC_EINVAL.
+ *   pool: cec_recovery_pool_begin queues the copy for the next flush of any kind, which makes
+ *     it in its one launch (no launch of its own) and, if it solves and the request is ready,
+ *     rebuilds the shards as for any request: in that launch up to three losses, by
+ *     ceil(n / 4) behind it past three.  _solve, _solve_host, _residual and _fold_update(s)
+ *     flush first, so an explicit solve or a _residual that finds the copy still queued is
+ *     that one flush launch (shared by every queued request) ahead of its own work.  As for a
+ *     queued reply, the copy reads the arena at the flush: call _fold_update(s) BEFORE the
+ *     diff is applied to the parity arena. */
 typedef struct cec_recovery cec_recovery;
 
 int cec_recovery_create(cec_recovery **out, int k, int m, const int *matrix, int lid_self,
@@ -437,7 +458,8 @@ int cec_recovery_pool_add_residuals(cec_recovery_pool *pool, const int *ids, con
  * residual has been given: the request can be solved.  A single loss: == complete. */
 int cec_recovery_pool_ready(const cec_recovery_pool *pool, int id);
 /* Fold every queued reply in one launch; returns the requests folded (>= 0): those with a
- * reply queued, not those a residual alone put into the pass. */
+ * reply queued, not those a residual alone put into the pass, nor those whose mask names no
+ * data lid and whose first touch (R = P) the pass makes. */
 int cec_recovery_pool_flush(cec_recovery_pool *pool, void *stream);
 /* The same call also solves every queued request that it makes ready -- by its last reply or
  * by its last residual: out[lost lid] (k device arenas by data lid, arena-addressed) =

@@ -2,8 +2,9 @@
 // header): the flush's slot layout and pattern keys, readiness and the all-or-nothing check
 // of a residual batch against brute force over random requests, and poolbook::Book -- the
 // pool's whole state machine -- over random schedules against a model that keeps the
-// reference's per-unit state.  Built with ASan + UBSan by tests/test_pool_losses_abi.py;
-// prints "ok".
+// reference's per-unit state, masks that name no data lid (k <= m) among them: such a request
+// holds R = P from begin, and no plan or accepted solve list may name a request that holds no
+// residual.  Built with ASan + UBSan by tests/test_pool_losses_abi.py; prints "ok".
 #include <cstdio>
 #include <cstdlib>
 #include <map>
@@ -185,6 +186,66 @@ static int queue_reuse() {
     return 0;
 }
 
+// Masks that name no data lid, step by step.  RS(1,1): the one mask {P0}, ready at begin and
+// solved by the next solving flush, in its launch.  RS(2,2) {P0, P1} led by P0: folded (R = P)
+// by a pass that comes before P1's residual, solved by the pass after it; and with the
+// residual first, both in one launch under a key of its own.
+static int no_data_lids() {
+    {
+        Book b(1, 1, 1, 4);
+        const int id = b.begin(0b10, 5, 5);
+        CHECK(id == 0 && b.complete(id) && b.ready(id) && !b.holds_residual(id));
+        CHECK(b.find(id)->touched && b.find(id)->touch_pending && b.queued_ids == std::vector<int>{0});
+        int bad = -1;
+        CHECK(b.check_solve(&id, 1, true, 0, &bad) == kIncomplete && bad == 0);  // (the pool flushes first)
+        CHECK(b.check_residual(id, 1) == kSingleLoss);
+        Plan pl = b.plan_flush(true, true, 0);
+        CHECK(pl.action == std::vector<char>{kFused} && pl.later.empty() && pl.planes == 1);
+        CHECK(b.commit_flush(pl, true) == 1 && b.queued_ids.empty());
+        CHECK(b.find(id)->solved && b.find(id)->solved_host && b.holds_residual(id) && !b.find(id)->touch_pending);
+        // the lost lid's diff moves R on; the explicit solve is accepted now
+        std::vector<Piece> pieces;
+        CHECK(b.pieces(b.touched_spans(), 5 * kUnit + 7, 100, 0, 0, pieces) == 1 && pieces.size() == 1);
+        CHECK(pieces[0].id == id && pieces[0].r_off == b.find(id)->slot * kUnit + 7 && pieces[0].len == 100);
+        CHECK(!b.find(id)->solved && b.ready(id));
+        CHECK(b.check_solve(&id, 1, true, 0, &bad) == kAccepted);
+        // a pass that does not solve makes the first touch alone; ended while it is owed: out of the queue
+        const int two = b.begin(0b10, 9, 10);
+        pl = b.plan_flush(false, false, 0);
+        CHECK(pl.action == std::vector<char>{kFold});
+        CHECK(b.commit_flush(pl, false) == 0 && b.holds_residual(two) && !b.find(two)->solved);
+        const int three = b.begin(0b10, 0, 0);
+        CHECK(b.queued_ids == std::vector<int>{three});
+        b.end(three);
+        CHECK(b.queued_ids.empty() && b.begin(0b10, 1, 1) == three && b.queued_ids == std::vector<int>{three});
+    }
+    for (int residual_first = 0; residual_first < 2; ++residual_first) {
+        Book b(2, 2, 2, 4);
+        const uint32_t mask = 0b1100;
+        const int id = b.begin(mask, 3, 4);
+        CHECK(id == 0 && b.complete(id) && !b.ready(id) && b.queued_ids == std::vector<int>{0});
+        CHECK(b.lost_lids(mask) == 0b11 && b.n_lost(mask) == 2 && needed(2, 2, mask) == 0b1000);
+        Plan pl;
+        if (!residual_first) {
+            pl = b.plan_flush(true, false, 0b11);
+            CHECK(pl.action == std::vector<char>{kFold});  // not ready: R = P alone
+            CHECK(b.commit_flush(pl, false) == 0 && b.holds_residual(id) && !b.find(id)->solved);
+        }
+        CHECK(b.check_residual(id, 3) == kAccepted && b.check_residual(id, 2) == kSelf);
+        b.note_residual(id, 3);
+        CHECK(b.ready(id) && b.queued_ids == std::vector<int>{0});
+        const bool touch = b.find(id)->touch_pending;
+        CHECK(touch == static_cast<bool>(residual_first));
+        pl = b.plan_flush(true, false, 0b01);  // shard 1 has no arena: not solved
+        CHECK(pl.action == std::vector<char>{touch ? kFold : kNothing});
+        pl = b.plan_flush(true, false, 0b11);
+        CHECK(pl.action == std::vector<char>{kFused} && pl.later.empty());
+        CHECK(flush_key(0, touch, true, mask, false) != flush_key(0, !touch, true, mask, false));
+        CHECK(b.commit_flush(pl, false) == 1 && b.find(id)->solved && b.holds_residual(id));
+    }
+    return 0;
+}
+
 static bool bit(uint32_t v, int j) { return j >= 0 && j < 32 && (v >> j & 1); }
 static auto fields(const Req &r) {
     return std::make_tuple(r.used, r.mask, r.ub, r.nunits, r.slot, r.touched, r.touch_pending, r.contributed, r.queued,
@@ -224,6 +285,19 @@ struct Schedule {
     std::vector<int> free_ids;
 
     bool live(int id) const { return id >= 0 && id < static_cast<int>(reqs.size()) && reqs[id].live; }
+    // A mask that names no data lid (k <= m): the request holds R = P from begin, so its units
+    // are touched from then on; the copy itself is owed to the next flush, as a first reply's is.
+    bool no_data(int id) const { return (reqs[id].mask & ((1u << k) - 1)) == 0; }
+    bool touch_owed(int id) const { return reqs[id].touches == 0 && (reqs[id].replied || no_data(id)); }
+    // Every unit of the request holds a residual (P, or P and replies), queued or made ...
+    bool holds(int id) const {
+        if (!live(id)) return false;
+        for (int s = reqs[id].slot; s < reqs[id].slot + reqs[id].n; ++s)
+            if (!touched[s]) return false;
+        return true;
+    }
+    // ... and made: a flush has written it to the slots.
+    bool in_place(int id) const { return holds(id) && reqs[id].touches == 1; }
     bool complete(int id) const {
         if (!live(id)) return false;
         for (int s = reqs[id].slot; s < reqs[id].slot + reqs[id].n; ++s)
@@ -284,6 +358,8 @@ struct Schedule {
             CHECK(b.lost_lids(r.mask) == l);
             CHECK(q->solved == r.solved && (!r.solved || q->solved_host == r.host));
             CHECK(q->enqueued == r.news);
+            CHECK(q->touch_pending == touch_owed(id) && b.holds_residual(id) == in_place(id));
+            CHECK(!complete(id) || holds(id));  // nothing complete without a residual
         }
         CHECK(b.find(-1) == nullptr && b.find(static_cast<int>(reqs.size())) == nullptr);
         CHECK(owner == occ && owner == b.slot_owner && b.active() == n_live && b.capacity() == cap);
@@ -297,10 +373,8 @@ struct Schedule {
 
     int begin() {
         int nl;
-        // 1 .. min(k - 1, m) losses, so every mask names a data lid: a mask that names none is
-        // complete at once and never touched, the open defect of a solve over an R that never
-        // received P (cec_poolbook.hpp, Book::ready), whose fix and test are their own change
-        uint32_t mask = random_mask(k, m, self, &nl, std::min(k - 1, m));
+        // 1 .. min(k, m) losses: with k <= m, masks that name no data lid among them
+        uint32_t mask = random_mask(k, m, self, &nl, std::min(k, m));
         int ub = rnd(0, 40), n = rnd(1, 5);
         const Book before = b;
         if (!rnd(0, 14)) {  // refused arguments
@@ -331,16 +405,19 @@ struct Schedule {
             reqs.emplace_back();
         }
         CHECK(id == want);
-        CHECK(std::find(b.queued_ids.begin(), b.queued_ids.end(), id) == b.queued_ids.end());
+        R r;
+        r.live = true, r.mask = mask, r.ub = ub, r.n = n;
+        reqs[id] = r;
+        // in the queue at once, once, exactly if its first touch waits for no reply
+        reqs[id].news = no_data(id);
+        CHECK(std::count(b.queued_ids.begin(), b.queued_ids.end(), id) == (no_data(id) ? 1 : 0));
         const Req *q = b.find(id);
         CHECK(q && q->slot >= 0 && q->slot + n <= cap);
+        reqs[id].slot = q->slot;
         for (int s = q->slot; s < q->slot + n; ++s) {
             CHECK(occ[s] < 0);
-            occ[s] = id, unit[s] = ub + (s - q->slot), touched[s] = 0, fed[s] = 0;
+            occ[s] = id, unit[s] = ub + (s - q->slot), touched[s] = no_data(id), fed[s] = 0;
         }
-        R r;
-        r.live = true, r.mask = mask, r.ub = ub, r.n = n, r.slot = q->slot;
-        reqs[id] = r;
         return 0;
     }
 
@@ -424,11 +501,14 @@ struct Schedule {
             const R &r = reqs[queue[x]];
             const Req &q = *b.find(queue[x]);
             // folds exactly the lids replied since the last flush; the first touch once
-            CHECK(q.queued == r.replied && q.touch_pending == (r.replied && r.touches == 0));
+            // (a mask without data lids owes its first touch without one)
+            CHECK(q.queued == r.replied && q.touch_pending == touch_owed(queue[x]));
             const bool solve = solves && ready(queue[x]) && has_outputs(queue[x], to_host, arenas);
             const int n = static_cast<int>(lost(queue[x]).size());
-            const Action want = solve && n <= 3 ? kFused : r.replied ? kFold : kNothing;
+            const Action want = solve && n <= 3 ? kFused : r.replied || touch_owed(queue[x]) ? kFold : kNothing;
             CHECK(pl.action[x] == want);
+            // solved by this pass: from a residual in place, or one this very launch makes
+            if (solve) CHECK(holds(queue[x]) && (in_place(queue[x]) || (touch_owed(queue[x]) && want != kNothing)));
             if (solve && n >= 4) later.push_back(queue[x]);
             if (want == kFused) ++fused;
             if (want == kFused && to_host) planes = std::max(planes, n);
@@ -442,7 +522,7 @@ struct Schedule {
         b.mark_solved(pl.later, to_host);  // (pool_solve_run behind the launch)
         for (size_t x = 0; x < queue.size(); ++x) {
             R &r = reqs[queue[x]];
-            if (r.replied && r.touches == 0) ++r.touches;
+            if (touch_owed(queue[x])) ++r.touches;
             r.replied = 0;
             r.news = false;
             if (pl.action[x] == kFused || std::count(later.begin(), later.end(), queue[x])) r.solved = true, r.host = to_host;
@@ -471,6 +551,7 @@ struct Schedule {
         int bad = -1;
         CHECK(b.check_solve(ids.data(), n, to_host, arenas, &bad) == want && bad == want_bad && same(b, before));
         if (want) return 0;
+        for (int id : ids) CHECK(in_place(id));  // no accepted list reads slots that hold no residual
         b.mark_solved(ids, to_host);
         for (int id : ids) reqs[id].solved = true, reqs[id].host = to_host;
         return 0;
@@ -555,7 +636,7 @@ static int schedules() {
     for (int round = 0; round < 2000; ++round) {
         rng.seed(0xB00C0000u + round);
         Schedule s;
-        s.k = rnd(2, kMaxK), s.m = rnd(1, kMaxM), s.self = rnd(s.k, s.k + s.m - 1), s.cap = rnd(1, 24);
+        s.k = rnd(1, kMaxK), s.m = rnd(1, kMaxM), s.self = rnd(s.k, s.k + s.m - 1), s.cap = rnd(1, 24);
         if (s.run(rnd(200, 400))) {
             std::printf("schedule %d: RS(%d,%d), self %d, capacity %d\n", round, s.k, s.m, s.self, s.cap);
             return 1;
@@ -565,7 +646,7 @@ static int schedules() {
 }
 
 int main() {
-    if (slots() || readiness_and_batches() || keys() || queue_reuse() || schedules()) return 1;
+    if (slots() || readiness_and_batches() || keys() || queue_reuse() || no_data_lids() || schedules()) return 1;
     std::printf("ok\n");
     return 0;
 }

@@ -110,6 +110,28 @@ def all_masks(k: int, m: int) -> list:
     return [mask for n in range(1, min(k, m) + 1) for mask in masks_of(k, m, n)]
 
 
+def no_data_masks(k: int, m: int) -> list:
+    """The C(m, k) masks that name no data lid (k <= m; none otherwise): every data shard
+    lost, k parities rebuild them.  The parity sets in lexicographic order, as masks_of(k, m,
+    k) lists them."""
+    return masks_of(k, m, k) if k <= m else []
+
+
+def session_sets(k: int, m: int) -> list:
+    """loss_sets carried on to n = min(k, m) for the codes with k <= m: for each n the lowest
+    n data lids lost with the lowest n parities, and the highest n with the highest n.  At
+    n = k both lose every data lid: the no-data masks of the lowest and of the highest k
+    parities (one mask if k == m)."""
+    assert k <= m, (k, m)
+    out = []
+    for n in range(1, k + 1):
+        for mask in (mask_of(k, range(n), range(k, k + n)),
+                     mask_of(k, range(k - n, k), range(k + m - n, k + m))):
+            if mask not in out:
+                out.append(mask)
+    return out
+
+
 def loss_sets(k: int, m: int) -> list:
     """The deterministic subset the session tests run: for each n in 1..min(m, k - 1) the
     lowest n data lids lost with the lowest n parities, and the highest n with the highest n.

@@ -80,13 +80,55 @@ def test_loss_sets():
             assert k - n >= 1 and mask in rc.masks_of(k, m, n)
 
 
-@pytest.mark.parametrize("k,m", [(3, 2), (6, 4)])
+def test_no_data_masks_and_session_sets():
+    """no_data_masks: the C(m, k) masks of k parities and no data lid, in masks_of's order,
+    none where k > m.  session_sets: two masks per loss count up to n = k, the last two (one
+    if k == m) no-data masks; below n = k it is loss_sets."""
+    for k, m in ((1, 1), (1, 2), (2, 2), (2, 3), (3, 4), (4, 8), (5, 8), (8, 8)):
+        nd = rc.no_data_masks(k, m)
+        assert len(nd) == len(set(nd)) == math.comb(m, k) and nd == rc.no_data_masks(k, m)
+        for mask in nd:
+            assert mask & ((1 << k) - 1) == 0 and bin(mask).count("1") == k and mask < 1 << (k + m)
+            assert rc.lost_of(k, mask) == list(range(k)) and rc.surviving_of(k, mask) == []
+        assert nd == sorted(nd, key=lambda mk: rc.pars_of(k, m, mk))  # lexicographic parity sets
+        assert [mk for mk in rc.all_masks(k, m) if not rc.surviving_of(k, mk)] == nd
+        sets = rc.session_sets(k, m)
+        assert len(sets) == len(set(sets)) == 2 * k - (k == m)
+        assert sorted({len(rc.lost_of(k, s)) for s in sets}) == list(range(1, k + 1))
+        assert [s for s in sets if len(rc.lost_of(k, s)) < k] == rc.loss_sets(k, m)
+        assert [s for s in sets if len(rc.lost_of(k, s)) == k] == ([nd[0]] if k == m else [nd[0], nd[-1]])
+    assert rc.no_data_masks(2, 2) == [0b1100] and rc.no_data_masks(8, 8) == [0xFF00]
+    assert rc.no_data_masks(1, 2) == [0b010, 0b100]
+    assert rc.no_data_masks(3, 2) == [] and rc.no_data_masks(6, 4) == []
+    assert len(rc.no_data_masks(4, 8)) == 70 and len(rc.no_data_masks(5, 8)) == 56
+    assert rc.session_sets(2, 2) == [0b0110, 0b1001, 0b1100]
+
+
+EVERY_MASK = {(3, 2): 9, (6, 4): 209, (1, 2): 2, (2, 2): 5, (2, 3): 9, (3, 4): 34, (4, 8): 494}
+
+
+@pytest.mark.parametrize("k,m", list(EVERY_MASK))
 def test_every_mask_solves(oracle, k, m):
-    """Every mask of RS(3,2) (9) and RS(6,4) (209): solve_lost returns the data."""
+    """Every mask of RS(3,2) (9) and RS(6,4) (209), and of the k <= m codes RS(1,2) (2),
+    RS(2,2) (5), RS(2,3) (9), RS(3,4) (34) and RS(4,8) (494), whose masks of k losses name no
+    data lid: solve_lost returns the data."""
     mat, data, parity = code_case(oracle, k, m)
     masks = rc.all_masks(k, m)
-    assert len(masks) == {(3, 2): 9, (6, 4): 209}[(k, m)]
+    assert len(masks) == EVERY_MASK[(k, m)]
+    if k <= m:
+        assert set(rc.no_data_masks(k, m)) <= set(masks) and rc.no_data_masks(k, m)
     for mask in masks:
+        check_mask(mat, k, m, mask, data, parity)
+
+
+def test_loss_sets_and_the_no_data_mask_solve_rs88(oracle):
+    """RS(8,8): loss_sets (one to seven lost) and 0xFF00, all eight shards from the eight
+    parities alone."""
+    k, m = 8, 8
+    mat, data, parity = code_case(oracle, k, m)
+    sets = rc.loss_sets(k, m) + [0xFF00]
+    assert len(sets) == 15 and rc.no_data_masks(k, m) == [0xFF00] and sets == rc.session_sets(k, m)
+    for mask in sets:
         check_mask(mat, k, m, mask, data, parity)
 
 
