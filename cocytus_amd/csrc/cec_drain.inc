@@ -17,7 +17,9 @@
 //   * the fold is cec_apply_diffs' kernel (pattern j: parity ^= MATRIX(self, j) * diff);
 //   * with live digests attached (cec_drainer_set_digests) each round ends with one
 //     digest_update_kernel launch (cec_digest.inc) over the round's whole tile list, behind
-//     its fold launches and reading the same staging: its atomics need no overlap waves.
+//     its fold launches and reading the same staging: its atomics need no overlap waves;
+//   * diffs received straight into the pinned staging area are folded from where they lie, and
+//     a batch that mixes such diffs with others never packs over them (drainer_apply_mixed).
 #include <memory>
 
 constexpr size_t kRoundBytes = size_t(16) << 20;  // pipelining granularity
@@ -119,9 +121,14 @@ CEC_API uint8_t *cec_drainer_staging(cec_drainer *d, size_t *capacity) {
 }
 
 // The per-update checks cec_drainer_apply makes before it touches anything (host only).
-static int drainer_check(const cec_drainer *d, const cec_host_update *u, int n, const char *op) {
+// *staged (where asked for, in the same pass): some non-empty update's buffer shares a byte
+// with the staging area.
+static int drainer_check(const cec_drainer *d, const cec_host_update *u, int n, const char *op,
+                         bool *staged = nullptr) {
     if (!d || n < 0 || (n > 0 && !u)) return fail(CEC_EINVAL, "%s: bad args", op);
+    if (staged) *staged = false;
     for (int i = 0; i < n; ++i) {
+        if (staged && !*staged) *staged = meets_area(u[i].buf, u[i].len, d->h_stage.get(), 2 * d->half);
         if (u[i].src_lid >= static_cast<uint32_t>(d->code.k) || (u[i].len && !u[i].buf))
             return fail(CEC_EINVAL, "%s: update %d: src_lid %u / buf", op, i, u[i].src_lid);
         if (u[i].len > d->half)
@@ -182,13 +189,15 @@ static int drainer_apply_in_place(cec_drainer *d, const cec_host_update *u,
     return CEC_OK;
 }
 
-// A small window (the caller checked the bounds): one pass of the caller's thread packs the
-// updates into the mapped staging and writes the tile list beside it; the kernel reads both
-// in place; the completion is the signal-kernel spin (stream_wait), fenced when the arena is
-// host memory (a registered ecmem).  Against the pack-thread path it saves the threads'
-// wake-up, two uploads and a hipStreamSynchronize: ~15 us instead of ~45-60 per window.
+// A small window, order[first, last) (the caller checked the bounds): one pass of the caller's
+// thread packs the updates into the mapped staging and writes the tile list beside it; the
+// kernel reads both in place; the completion is the signal-kernel spin (stream_wait), fenced
+// when the arena is host memory (a registered ecmem).  Against the pack-thread path it saves
+// the threads' wake-up, two uploads and a hipStreamSynchronize: ~15 us instead of ~45-60 per
+// window.
 static int drainer_apply_small(cec_drainer *d, const cec_host_update *u, const std::vector<int> &order,
-                               const std::vector<int> &wave, uint8_t *parity, int dev, hipStream_t s) {
+                               size_t first, size_t last, const std::vector<int> &wave, uint8_t *parity, int dev,
+                               hipStream_t s) {
     if (!d->smt && (!d->sm.acquire_mapped(dev, kDrainSmallBytes) ||
                     !d->smt.acquire_mapped(dev, kDrainSmallTiles * sizeof(Tile)))) {
         d->sm.release();
@@ -196,7 +205,8 @@ static int drainer_apply_small(cec_drainer *d, const cec_host_update *u, const s
     }
     size_t so = 0;
     WaveTiles wt(d->smt.get<Tile>());
-    for (int i : order) {
+    for (size_t p = first; p < last; ++p) {
+        const int i = order[p];
         const cec_host_update &x = u[i];
         wt.enter(wave[i]);
         if (x.len) memcpy(d->sm.get() + so, x.buf, x.len);
@@ -208,10 +218,54 @@ static int drainer_apply_small(cec_drainer *d, const cec_host_update *u, const s
     return stream_wait(s, !classify(parity).device_memory());  // applied: the caller may ack / reuse its buffers
 }
 
+// The apply order of a batch: its overlap waves (wave[i]: update i's), then the list order.
+static void wave_order(const cec_host_update *u, int n, std::vector<int> &wave, std::vector<int> &order) {
+    const int n_waves = overlap_waves(u, n, wave);
+    order.resize(n);
+    for (int i = 0; i < n; ++i) order[i] = i;
+    if (n_waves > 1)
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return wave[a] < wave[b]; });
+}
+
+// A batch above the small window of which some diffs lie in the staging area and some do not.
+// The pack path cannot take it: it packs into that very area, over diffs it has yet to read.
+// Applied as two parts on the stream, each with its own waves (XOR accumulation commutes and
+// the parts run in stream order, so the bytes are the sequential loop's): the diffs in the
+// area in place, then the others through the small path's own mapped staging, one window of
+// it after another.  Nothing is written to the staging area.  A mixed batch is the rare one
+// (a diff too large for the receive buffers, malloc'd by the server): the windows complete one
+// by one, without the pack path's overlap of copy and fold.
+static int drainer_apply_mixed(cec_drainer *d, const cec_host_update *u, int n, uint8_t *parity, int dev,
+                               hipStream_t s) {
+    std::vector<cec_host_update> in, rest;
+    uint64_t lo, hi;
+    split_by_area(u, n, d->h_stage.get(), 2 * d->half, static_cast<uint32_t>(kDrainSmallBytes), in, rest, &lo, &hi);
+    std::vector<int> wave, order;
+    HIP_TRY(d->pipe.wait_all());
+    if (hi > lo)  // (none wholly inside: a buffer that only partly lies in the area)
+        HIP_TRY(hipMemcpyAsync(d->d_stage.get() + lo, d->h_stage.get() + lo, hi - lo, hipMemcpyHostToDevice, s));
+    wave_order(in.data(), static_cast<int>(in.size()), wave, order);
+    if (int r = drainer_apply_in_place(d, in.data(), order, wave, parity, dev, s)) return r;  // (synchronised)
+    wave_order(rest.data(), static_cast<int>(rest.size()), wave, order);
+    for (size_t next = 0; next < order.size();) {
+        const size_t first = next;
+        size_t bytes = 0, tiles = 0;
+        for (; next < order.size(); ++next) {  // (a piece always fits: <= kDrainSmallBytes, so <= 257 tiles)
+            const cec_host_update &x = rest[order[next]];
+            bytes += (x.len + 15) & ~static_cast<size_t>(15);
+            tiles += tiles_of(x.addr, x.len);
+            if (next > first && (bytes > kDrainSmallBytes || tiles > kDrainSmallTiles)) break;
+        }
+        if (int r = drainer_apply_small(d, rest.data(), order, first, next, wave, parity, dev, s)) return r;
+    }
+    return CEC_OK;
+}
+
 CEC_API int cec_drainer_apply(cec_drainer *d, const cec_host_update *u, int n, uint8_t *parity,
                               void *stream) {
     if (!parity) return fail(CEC_EINVAL, "cec_drainer_apply: parity is NULL");
-    if (int r = drainer_check(d, u, n, "cec_drainer_apply")) return r;
+    bool staged;
+    if (int r = drainer_check(d, u, n, "cec_drainer_apply", &staged)) return r;
     d->last_launches = 0;
     if (n == 0) return CEC_OK;
     int dev;
@@ -227,7 +281,7 @@ CEC_API int cec_drainer_apply(cec_drainer *d, const cec_host_update *u, int n, u
     for (int i = 0; i < n && in_place; ++i) {
         if (!u[i].len) continue;
         const uint8_t *b = static_cast<const uint8_t *>(u[i].buf);
-        in_place = b >= h_stage && b + u[i].len <= h_stage + 2 * d->half;
+        in_place = inside_area(b, u[i].len, h_stage, 2 * d->half);
         lo = std::min<uint64_t>(lo, b - h_stage);
         hi = std::max<uint64_t>(hi, b - h_stage + u[i].len);
     }
@@ -238,12 +292,8 @@ CEC_API int cec_drainer_apply(cec_drainer *d, const cec_host_update *u, int n, u
         HIP_TRY(d->pipe.wait_all());
         if (hi > lo) HIP_TRY(hipMemcpyAsync(d_stage + lo, h_stage + lo, hi - lo, hipMemcpyHostToDevice, s));
     }
-    std::vector<int> wave;
-    const int n_waves = overlap_waves(u, n, wave);
-    std::vector<int> order(n);
-    for (int i = 0; i < n; ++i) order[i] = i;
-    if (n_waves > 1)
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return wave[a] < wave[b]; });
+    std::vector<int> wave, order;
+    wave_order(u, n, wave, order);
 
     if (in_place) {
         if (int r = drainer_apply_in_place(d, u, order, wave, parity, dev, s)) return r;
@@ -257,10 +307,16 @@ CEC_API int cec_drainer_apply(cec_drainer *d, const cec_host_update *u, int n, u
             tiles += tiles_of(u[i].addr, u[i].len);
         }
         if (bytes <= kDrainSmallBytes && tiles <= kDrainSmallTiles) {
-            if (int r = drainer_apply_small(d, u, order, wave, parity, dev, s)) return r;
+            if (int r = drainer_apply_small(d, u, order, 0, order.size(), wave, parity, dev, s)) return r;
             guard.dismiss();
             return CEC_OK;
         }
+    }
+    // The pack path writes the staging area: no diff it has yet to read may lie there.
+    if (staged) {
+        if (int r = drainer_apply_mixed(d, u, n, parity, dev, s)) return r;
+        guard.dismiss();
+        return CEC_OK;
     }
 
     std::vector<CopyItem> items;

@@ -9,6 +9,7 @@
 //   radix_sort              (key, index) pairs by key
 //   colour_intervals        start-sorted intervals into overlap-free waves
 //   overlap_waves           the drainer's waves of a batch of updates
+//   inside_area / split_by_area   a drainer batch against the drainer's own staging area
 //   Hb* / hb_cluster_waves  the host batch's pieces, clusters and waves
 #pragma once
 
@@ -221,6 +222,43 @@ inline int overlap_waves(const cec_host_update *u, int n, std::vector<int> &wave
             return std::pair<uint64_t, uint64_t>(v.addr, v.addr + v.len);
         },
         [&](size_t i, int w) { wave[byaddr[i].second] = w; });
+}
+
+// A host buffer [b, b + len) against an area [base, base + cap), compared as integers (the
+// two need not be one object): wholly inside it; sharing at least one byte with it.
+inline bool inside_area(const void *b, size_t len, const void *base, size_t cap) {
+    const uintptr_t p = reinterpret_cast<uintptr_t>(b), a = reinterpret_cast<uintptr_t>(base);
+    return p >= a && len <= cap && p - a <= cap - len;
+}
+inline bool meets_area(const void *b, size_t len, const void *base, size_t cap) {
+    const uintptr_t p = reinterpret_cast<uintptr_t>(b), a = reinterpret_cast<uintptr_t>(base);
+    return len && p < a + cap && p + len > a;
+}
+
+// The two parts of a drainer batch that mixes diffs received in the staging area with diffs
+// elsewhere: `in` takes the non-empty updates wholly inside [base, base + cap), `rest` every
+// other non-empty one (a buffer that only partly lies in the area included), cut into pieces
+// of at most `piece` bytes.  Both keep the list order; [*lo, *hi) receives the span of the
+// area that `in` uses.
+inline void split_by_area(const cec_host_update *u, int n, const void *base, size_t cap, uint32_t piece,
+                          std::vector<cec_host_update> &in, std::vector<cec_host_update> &rest, uint64_t *lo,
+                          uint64_t *hi) {
+    in.clear();
+    rest.clear();
+    *lo = UINT64_MAX, *hi = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!u[i].len) continue;
+        const uint8_t *b = static_cast<const uint8_t *>(u[i].buf);
+        if (inside_area(b, u[i].len, base, cap)) {
+            const uint64_t at = reinterpret_cast<uintptr_t>(b) - reinterpret_cast<uintptr_t>(base);
+            *lo = std::min<uint64_t>(*lo, at);
+            *hi = std::max<uint64_t>(*hi, at + u[i].len);
+            in.push_back(u[i]);
+            continue;
+        }
+        for (uint32_t o = 0; o < u[i].len; o += std::min(piece, u[i].len - o))
+            rest.push_back(cec_host_update{b + o, u[i].addr + o, std::min(piece, u[i].len - o), u[i].src_lid});
+    }
 }
 
 // ---------------------------------------------------------------- the host batch's plan

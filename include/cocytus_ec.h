@@ -214,7 +214,8 @@ uint32_t cec_recovery_mask(int k, int m, int leader_lid, const int *connected);
  * Replaces the drain loops `while (done_xid < stable_xid) process_rep_command(...)`
  * (memcached.c:4231, 4322, 4350, 8068) with one call per batch of pending diffs. */
 typedef struct cec_host_update {   /* one pending rep_queue_item (rep_queue.h:28-39) */
-    const void *buf;               /* e->vbuf: the shipped diff, host memory (any kind) */
+    const void *buf;               /* e->vbuf: the shipped diff, host memory (any kind; inside
+                                    * cec_drainer_staging or not, in any mix within one batch) */
     uint64_t addr;                 /* e->addr: arena offset (replayed ecalloc address) */
     uint32_t len;                  /* it->nbytes */
     uint32_t src_lid;              /* data shard lid the diff came from (0..k-1) */
@@ -269,7 +270,14 @@ int cec_drainer_set_digests(cec_drainer *d, uint8_t *digests, uint64_t n_units);
  * A server can receive diffs straight into it (conn_nread of the "rep" payload,
  * memcached.c:7727-7735, into e->vbuf carved from this area).  When every update of a
  * cec_drainer_apply call points into it, the call skips the pack copy: one H2D of the
- * used span, then the fold.  The caller must not write the area during an apply. */
+ * used span, then the fold.  A batch that mixes updates inside the area with updates
+ * elsewhere is applied as well: the ones wholly inside it in place, the others (a buffer
+ * that lies only partly in the area among them) from a copy in staging of the library's
+ * own; above 1 MiB of diffs or 8192 tiles such a batch completes in several synchronous
+ * steps, so a server that wants the pipelined pack path keeps a batch on one side.
+ * The caller must not write the area during an apply, and the library never writes over
+ * an update's source that lies in it: on return every such source holds what the caller
+ * put there. */
 uint8_t *cec_drainer_staging(cec_drainer *d, size_t *capacity);
 
 /* ---- galois_w08_region_multiply, batched, over host memory ----

@@ -4,7 +4,8 @@
 // ASan + UBSan.  No two overlapping updates may share a wave; a batch of distinct values is
 // one wave; without empty updates the wave count is the deepest overlap; the address sort
 // is ordered.  The same colouring over unit-aligned tile intervals, as the recovery pool's
-// fold_updates feeds it, has the same two properties.
+// fold_updates feeds it, has the same two properties.  Last, a batch against the drainer's own
+// staging area (inside_area, meets_area, split_by_area): check_areas below.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -25,6 +26,67 @@ static int depth_of(const std::vector<uint64_t> &lo, const std::vector<uint64_t>
         depth = std::max(depth, d);
     }
     return depth;
+}
+
+// A batch against the drainer's staging area (addresses only: nothing is dereferenced).  An
+// area of 8192 bytes at 1 MiB: a buffer is inside it from its first byte to one that ends on
+// its last; one byte before or one byte beyond is outside but meets it; split_by_area sends
+// the first kind to `in` with their span, every other non-empty one to `rest` in pieces of at
+// most `piece` bytes that tile it exactly, both in list order.
+static int check_areas() {
+    const uintptr_t base = 1u << 20;
+    const size_t cap = 8192;
+    auto at = [&](long off) { return reinterpret_cast<const void *>(base + off); };
+    struct { long off; size_t len; bool inside, meets; } probe[] = {
+        {0, 1, true, true},       {0, 8192, true, true},   {8191, 1, true, true},    {4096, 4096, true, true},
+        {-1, 2, false, true},     {-1, 1, false, false},   {8191, 2, false, true},   {8192, 1, false, false},
+        {-100, 9000, false, true}, {0, 8193, false, true}, {-5000, 4096, false, false}, {100, 0, true, false},
+        {-1, 0, false, false},
+    };
+    for (const auto &p : probe) {
+        if (inside_area(at(p.off), p.len, at(0), cap) != p.inside) return 1;
+        if (meets_area(at(p.off), p.len, at(0), cap) != p.meets) return 2;
+    }
+    std::mt19937_64 r(11);
+    for (int t = 0; t < 2000; ++t) {
+        const int n = 1 + r() % 40;
+        const uint32_t piece = 1 + r() % 5000;
+        std::vector<cec_host_update> u(n), in, rest;
+        for (auto &x : u) {
+            x.len = r() % 5 ? static_cast<uint32_t>(r() % 12000) : 0;
+            x.buf = at(static_cast<long>(r() % 24000) - 8000);
+            x.addr = r() % (1ull << 34);
+            x.src_lid = r() % 3;
+        }
+        uint64_t lo, hi;
+        split_by_area(u.data(), n, at(0), cap, piece, in, rest, &lo, &hi);
+        size_t ii = 0, ri = 0;
+        uint64_t want_lo = UINT64_MAX, want_hi = 0;
+        for (const auto &x : u) {
+            if (!x.len) continue;
+            const uintptr_t b = reinterpret_cast<uintptr_t>(x.buf);
+            if (b >= base && b + x.len <= base + cap) {
+                if (ii >= in.size() || in[ii].buf != x.buf || in[ii].addr != x.addr || in[ii].len != x.len ||
+                    in[ii].src_lid != x.src_lid)
+                    return 3;
+                ++ii;
+                want_lo = std::min<uint64_t>(want_lo, b - base);
+                want_hi = std::max<uint64_t>(want_hi, b - base + x.len);
+                continue;
+            }
+            for (uint32_t o = 0; o < x.len;) {  // its pieces, in order, none empty, none above `piece`
+                if (ri >= rest.size()) return 4;
+                const cec_host_update &p = rest[ri++];
+                if (reinterpret_cast<uintptr_t>(p.buf) != b + o || p.addr != x.addr + o || p.src_lid != x.src_lid) return 5;
+                if (!p.len || p.len > piece || p.len > x.len - o) return 6;
+                if (p.len < piece && o + p.len != x.len) return 7;  // (only the last may be short)
+                o += p.len;
+            }
+        }
+        if (ii != in.size() || ri != rest.size()) return 8;
+        if (lo != want_lo || hi != want_hi) return 9;
+    }
+    return 0;
 }
 
 int main() {
@@ -91,5 +153,6 @@ int main() {
     radix_sort(s);
     for (size_t i=1;i<s.size();++i) if (s[i-1].first > s[i].first) { printf("not sorted\n"); return 1; }
     for (size_t i=0;i<s.size();++i) if (u[s[i].second].addr != s[i].first) { printf("index lost\n"); return 1; }
+    if (int bad = check_areas()) { printf("area check %d\n", bad); return 1; }
     printf("ok\n");
 }

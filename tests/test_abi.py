@@ -358,5 +358,8 @@ def test_drain_wave_colouring(tmp_path):
     header by tests/drain_c/waves_main.cpp and run under ASan + UBSan on 4,000 random
     batches: overlapping updates never share a launch wave, distinct values take one, a
     batch without empty updates takes exactly its overlap depth; and on 2,000 sets of
-    unit-aligned tile intervals as the recovery pool's fold_updates feeds them, the same."""
+    unit-aligned tile intervals as the recovery pool's fold_updates feeds them, the same.
+    Also there: which updates of a batch lie in the drainer's staging area (a buffer one byte
+    before it, one byte beyond, ending on its last byte) and the two parts a mixed batch is
+    split into, on 2,000 random batches."""
     _run_hostplan_program(tmp_path, "waves_main")

@@ -22,8 +22,11 @@ grid is one workgroup per tile part, and under the automatic store policy a laun
 small stores write-through.  Bytes are compared with the oracle as in test_gpu_parity.py.
 
 Not reached: cec_drainer_apply's staged path (pack threads, two uploads per round) takes
-over above 1 MiB of packed diffs or 8192 tiles, which no input of this size comes near;
-test_drainer_matches_sequential_loop covers its bytes.
+over above 1 MiB of packed diffs or 8192 tiles, which no input of this size comes near.
+tests/test_gpu_drainer_paths.py runs it on both sides of each of those two limits, with the
+round cutting of the pack and in-place paths, batches that mix staged and pageable diffs,
+and arena offsets around 2^32; test_drainer_matches_sequential_loop covers its bytes on
+random batches.
 """
 from __future__ import annotations
 

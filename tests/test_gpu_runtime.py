@@ -551,7 +551,7 @@ def test_release_stream_refused_while_capturing(gpu, oracle):
     plan.destroy()
 
 
-@pytest.mark.parametrize("path", ["drain_small", "drain_pack", "host_batch", "pool_fold_updates"])
+@pytest.mark.parametrize("path", ["drain_small", "drain_pack", "drain_mixed", "host_batch", "pool_fold_updates"])
 def test_failed_later_wave_leaves_nothing_in_flight(gpu, oracle, path):
     """A launch that fails after earlier waves of the same call ran (fault injection:
     cec_internal_fail_launch(1) -- the second launch of the call fails as a HIP error
@@ -561,7 +561,10 @@ def test_failed_later_wave_leaves_nothing_in_flight(gpu, oracle, path):
     the first wave holds every distinct update once, whichever of the twin pair it took.
     Checked: the registered host arena holds exactly the first wave's bytes on return (read
     without a device sync), the host batch wrote no destination, the pool's residual holds
-    the first wave's folds; then the whole window again gives the reference's bytes."""
+    the first wave's folds; then the whole window again gives the reference's bytes.
+    drain_mixed: the first update and its twin stay in pageable memory and the other 399 lie in
+    the drainer's staging area, so the call's first launch is the in-place part and the failing
+    second one the first wave of the rest: every update but the first is applied on return."""
     torch, ec = gpu
     k, m, U = 3, 2, 4096
     mat = ec.coding_matrix(k, m)
@@ -581,6 +584,16 @@ def test_failed_later_wave_leaves_nothing_in_flight(gpu, oracle, path):
             alias = ec.host_register(arena)
             try:
                 with ec.Drainer(k, m, mat, lid_self, staging_bytes=8 << 20) as d:
+                    first, again = once, 2  # what the launch before the failure applies; launches of a whole call
+                    if path == "drain_mixed":
+                        base, view = d.staging()
+                        staged = []
+                        for i, (buf, addr, j) in enumerate(ups[1:n]):
+                            view[i * U:(i + 1) * U] = buf
+                            staged.append((base + i * U, addr, j, U))
+                        ups = [ups[0]] + staged + [ups[n]]
+                        first, again = once.copy(), 3  # (the in-place part, then the rest's two waves)
+                        first[0:U] = 0
                     ec.fail_launch(1)
                     seq = ec.last_launch()["seq"]
                     with pytest.raises(ec.CecError) as e:
@@ -588,10 +601,10 @@ def test_failed_later_wave_leaves_nothing_in_flight(gpu, oracle, path):
                     assert e.value.code == ec.CEC_EHIP
                     # exactly the first wave was launched: the failure hit the second
                     assert ec.last_launch()["seq"] == seq + 1
-                    assert np.array_equal(arena, before ^ once)  # wave 0 complete on return
-                    assert d.apply(ups, alias) == 2  # the whole window again: every update twice
-                    assert ec.last_launch()["seq"] == seq + 3  # (two waves, one launch each)
-                    exp = before.copy()   # but the first (three times in all)
+                    assert np.array_equal(arena, before ^ first)  # wave 0 complete on return
+                    assert d.apply(ups, alias) == again  # the whole window again: every update twice
+                    assert ec.last_launch()["seq"] == seq + 1 + again  # (one launch per wave)
+                    exp = before ^ first ^ once   # but the first (with its twin's: three times in all)
                     oracle.region_multiply(ups[0][0], c, exp[0:U], 1)
                     assert np.array_equal(arena, exp)
             finally:
