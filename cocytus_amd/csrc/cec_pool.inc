@@ -788,6 +788,9 @@ CEC_API int cec_recovery_pool_solve_host(cec_recovery_pool *p, const int *ids, i
 CEC_API int cec_recovery_pool_residual(cec_recovery_pool *p, int id, void *dst, void *stream) {
     const poolbook::Req *r = pool_find(p, id);
     if (!r || !dst) return fail(CEC_EINVAL, "cec_recovery_pool_residual: request %d / dst", id);
+    // no reply ever queued (a mask without data lids is touched from begin): R[slot] holds what
+    // the slots' previous owner left, and check_solve refuses such a request too
+    if (!r->touched) return fail(CEC_EINVAL, "cec_recovery_pool_residual: request %d holds no residual yet", id);
     if (int rc = cec_recovery_pool_flush(p, stream); rc < 0) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     UseNote note_{p->uses, s};

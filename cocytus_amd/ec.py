@@ -812,7 +812,9 @@ class RecoveryPool:
         return rc
 
     def flush_solve(self, out_arenas, stream=None) -> int:
-        """flush(), also solving every single-loss request it completes into out_arenas."""
+        """flush(), also solving every queued request it makes ready, of any loss count, into
+        out_arenas (k arenas by data lid; a request that loses a lid whose arena is None is
+        folded only).  Returns the requests solved."""
         oo = (ctypes.c_void_p * self.k)(*[_ptr(out_arenas[j]) if j < len(out_arenas) and
                                           out_arenas[j] is not None else None for j in range(self.k)])
         rc = lib().cec_recovery_pool_flush_solve(self._h, oo, _stream(stream))
@@ -821,8 +823,8 @@ class RecoveryPool:
         return rc
 
     def flush_solve_host(self, stream=None) -> int:
-        """flush(), also solving every single-loss request it completes into the pool's
-        own host output (read with output())."""
+        """flush(), also solving every queued request it makes ready, of any loss count, into
+        the pool's own host planes (read with output(rid, x)).  Returns the requests solved."""
         rc = lib().cec_recovery_pool_flush_solve_host(self._h, _stream(stream))
         if rc < 0:
             _check(rc)

@@ -467,7 +467,9 @@ int cec_recovery_pool_add_residuals(cec_recovery_pool *pool, const int *ids, con
 int cec_recovery_pool_ready(const cec_recovery_pool *pool, int id);
 /* Fold every queued reply in one launch; returns the requests folded (>= 0): those with a
  * reply queued, not those a residual alone put into the pass, nor those whose mask names no
- * data lid and whose first touch (R = P) the pass makes. */
+ * data lid and whose first touch (R = P) the pass makes.  The pass empties the queue: a
+ * request that is ready after it is NOT solved by a later _flush_solve, which looks only at
+ * what has been queued since; cec_recovery_pool_solve / _solve_host solve it. */
 int cec_recovery_pool_flush(cec_recovery_pool *pool, void *stream);
 /* The same call also solves every queued request that it makes ready -- by its last reply or
  * by its last residual: out[lost lid] (k device arenas by data lid, arena-addressed) =
@@ -475,6 +477,10 @@ int cec_recovery_pool_flush(cec_recovery_pool *pool, void *stream);
  * launch (the residual and the shards are its four outputs); requests of n >= 4 losses are
  * folded by that launch and solved by ceil(n_max / 4) launches behind it, which read the
  * new residual from device memory.  A pass with nothing to fold has no fold launch.
+ * Only requests in the queue (a reply, a residual or a begin without data lids since the
+ * last flush of any kind) that are ready are solved, and of those only the ones whose lost
+ * lids all have an arena: out[j] may be NULL, and a ready request that loses such a lid is
+ * folded only and leaves the queue unsolved, for an explicit solve.
  * Returns the requests solved; cec_recovery_pool_solved tells which. */
 int cec_recovery_pool_flush_solve(cec_recovery_pool *pool, uint8_t *const *out, void *stream);
 /* 1 while the request's rebuilt bytes are current: a solve (fused or explicit) wrote them
@@ -484,7 +490,12 @@ int cec_recovery_pool_solved(const cec_recovery_pool *pool, int id);
 /* check_recovery_1st_completeness: every data lid of the request's mask applied or queued. */
 int cec_recovery_pool_complete(const cec_recovery_pool *pool, int id);
 /* recovery_try_update_unit for every request of the pool (flushes first); returns the
- * units folded (>= 0) or a negative cec_status. */
+ * units folded (>= 0) or a negative cec_status.  The diff is folded into every live request
+ * that holds a residual, meets [addr, addr + len) and has had no reply of peer_lid -- a lid
+ * the request has lost included (recovery.c:116-120) -- and requests over the same arena
+ * units each take it (each counts its units).  A request folded into is no longer solved
+ * (its rebuilt bytes are stale; _output is NULL) but stays ready and out of the queue: only
+ * an explicit solve rebuilds it again.  Given residuals never move. */
 int cec_recovery_pool_fold_update(cec_recovery_pool *pool, int peer_lid, uint64_t addr, const void *diff,
                                   uint32_t len, void *stream);
 /* The same for a drain window: every update u[i] (host buffers; any data lid) folded as
@@ -507,14 +518,20 @@ int cec_recovery_pool_solve(cec_recovery_pool *pool, const int *ids, int n, uint
  * are acquired on first use.  The bytes are fenced for the host when the call returns. */
 int cec_recovery_pool_flush_solve_host(cec_recovery_pool *pool, void *stream);
 int cec_recovery_pool_solve_host(cec_recovery_pool *pool, const int *ids, int n, void *stream);
-/* Request id's rebuilt bytes (*len = its units x 4 KiB) after a _host solve, while
- * cec_recovery_pool_solved(id) holds; NULL otherwise.  Valid until the request ends. */
+/* Request id's rebuilt bytes (*len = its units x 4 KiB) if its last solve was a _host one
+ * and cec_recovery_pool_solved(id) still holds; NULL otherwise (never solved, last solved
+ * into an arena, or folded into since).  Valid until the request ends. */
 const uint8_t *cec_recovery_pool_output(const cec_recovery_pool *pool, int id, size_t *len);
 /* The same for the x-th lost data lid of the request (x = 0: cec_recovery_pool_output). */
 const uint8_t *cec_recovery_pool_output_lost(const cec_recovery_pool *pool, int id, int x, size_t *len);
-/* Non-leader: copy request id's residual (its units x 4 KiB) to dst (host or device). */
+/* Non-leader: copy request id's residual (its units x 4 KiB) to dst (host or device);
+ * flushes first.  A live request that holds no residual -- its mask names data lids and no
+ * reply has ever been queued, so its slots still hold what their previous owner left -- is
+ * CEC_EINVAL with nothing copied and nothing flushed, as the solves refuse it. */
 int cec_recovery_pool_residual(cec_recovery_pool *pool, int id, void *dst, void *stream);
-/* recovery_req_remove: release the request's units. */
+/* recovery_req_remove: release the request's units.  A reply of its still queued is folded
+ * first (one flush of the whole queue); a request queued by a residual or by its begin alone
+ * just leaves the queue. */
 int cec_recovery_pool_end(cec_recovery_pool *pool, int id);
 int cec_recovery_pool_active(const cec_recovery_pool *pool);
 
