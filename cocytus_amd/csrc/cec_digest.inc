@@ -11,36 +11,23 @@
 // cec_digest_apply_diffs folds every applied diff into it (digest_update_launch, which the
 // drainer of cec_drain.inc calls once per round), and cec_digest_verify_region compares it
 // with a fresh one through the same check.
-// Built from the library's parts: a TileSource to walk, launch_countdown, scrub_patterns +
-// pattern_tables for the check's coefficients, the capacity ladder, record_launch.
+// Built from the library's parts: a TileSource to walk, the planners of cec_launchplan.hpp
+// (plan_digest, plan_digest_update, plan_digest_check), scrub_patterns for the check's
+// coefficients, enqueue_launch.
 
 namespace {
 
-// One dispatch holds 2^32 - 1 work items; a digest launch has one wave per (tile, arena).
-constexpr uint64_t kDigestMaxWork = 0xFFFFFFFFull / kBlock * (kBlock / 64);
-
-// Waves (work items) per workgroup, log2.  Four: a 256-lane workgroup whose waves each
-// take their own (tile, arena).  One-wave workgroups, the combine kernels' split of full
-// tiles, measured 10-12 % slower here (327,680 workgroups of 4 KiB each against 81,920:
-// DESIGN.md section 8).  CEC_DIGEST_WAVES_SHIFT=0..2 pins another (measurement).
-uint32_t digest_waves_shift() {
-    static const uint32_t shift = [] {
-        const char *e = getenv("CEC_DIGEST_WAVES_SHIFT");
-        return static_cast<uint32_t>(e && *e ? std::min(2, std::max(0, atoi(e))) : 2);
-    }();
-    return shift;
-}
-
 template <int NT, int LT>
-void launch_digest_check_k(const DigestCheckArgs &a, uint32_t grid, hipStream_t s) {
-    hipLaunchKernelGGL((digest_check_kernel<NT, LT>), dim3(grid), dim3(kBlock), 0, s, a);
+void launch_digest_check_k(const DigestCheckArgs &a, const LaunchPlan &lp, hipStream_t s) {
+    hipLaunchKernelGGL((digest_check_kernel<NT, LT>), dim3(lp.grid), dim3(lp.block), 0, s, a);
 }
 
-Capacity launch_digest_check(int k, int lt, const DigestCheckArgs &a, uint32_t grid, hipStream_t s) {
-#define CEC_DC(NT, LT)                            \
-    launch_digest_check_k<NT, LT>(a, grid, s);    \
-    return {NT, LT};
-    CEC_CAPACITY_RUNGS_FROM_4(k, lt, CEC_DC)
+// The plan's rung of the capacity ladder.
+void launch_digest_check(const DigestCheckArgs &a, const LaunchPlan &lp, hipStream_t s) {
+#define CEC_DC(NT, LT)                           \
+    launch_digest_check_k<NT, LT>(a, lp, s);    \
+    return;
+    CEC_CAPACITY_RUNGS_FROM_4(lp.nt, lp.lt, CEC_DC)
 #undef CEC_DC
 }
 
@@ -66,32 +53,30 @@ static int digest_common(const char *op, int n, const uint8_t *const *arenas, ui
     TileSource src;
     if (int r = plan ? TileSource::of_plan(plan, dev, &src) : TileSource::of_region(len, &src)) return r;
     t_last_engine = CEC_ENGINE_PERM;  // whatever cec_set_engine says
-    if (src.n_tiles == 0) return CEC_OK;
-    const uint64_t n_work = src.n_tiles * static_cast<uint64_t>(n);
-    if (n_work > kDigestMaxWork)
+    Launch l;
+    l.plan = plan_digest(n, src.n_tiles, g_knobs);
+    if (l.plan.refusal == kPlanNothing) return CEC_OK;  // (before the fail hook counts)
+    if (l.plan.refusal == kPlanTooLarge)
         return fail(CEC_EINVAL, "%s: %llu tiles x %d arenas, one launch holds %llu (tile, arena) pairs", op,
                     static_cast<unsigned long long>(src.n_tiles), n, static_cast<unsigned long long>(kDigestMaxWork));
-    if (int rc = launch_countdown()) return rc;
+    l.uses[0] = src.uses;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    DigestArgs a;
-    memset(&a, 0, sizeof a);
-    for (int i = 0; i < n; ++i) {
-        a.base[i] = arenas[i];
-        a.out[i] = digests[i];
-    }
-    a.tiles = src.tiles;
-    a.implicit_len = src.implicit_len;
-    a.n_tiles = static_cast<uint32_t>(src.n_tiles);
-    a.n = static_cast<uint32_t>(n);
-    a.n_work = static_cast<uint32_t>(n_work);
-    a.waves_shift = digest_waves_shift();
-    const uint32_t per_wg = 1u << a.waves_shift;
-    const uint32_t grid = static_cast<uint32_t>((n_work + per_wg - 1) / per_wg);
-    hipLaunchKernelGGL(digest_kernel, dim3(grid), dim3(64u << a.waves_shift), 0, stream, a);
-    if (src.uses) src.uses->note(stream);
-    HIP_TRY(hipGetLastError());
-    record_launch(CEC_KERNEL_DIGEST, {n, 0}, kAccNone, false, 0, 0, grid, src.n_tiles, 0);
-    return CEC_OK;
+    return enqueue_launch(dev, stream, l, [&](const LaunchPlan &lp, const uint8_t *) {
+        DigestArgs a;
+        memset(&a, 0, sizeof a);
+        for (int i = 0; i < n; ++i) {
+            a.base[i] = arenas[i];
+            a.out[i] = digests[i];
+        }
+        a.tiles = src.tiles;
+        a.implicit_len = src.implicit_len;
+        a.n_tiles = static_cast<uint32_t>(src.n_tiles);
+        a.n = static_cast<uint32_t>(n);
+        a.n_work = a.n_tiles * a.n;  // (<= kDigestMaxWork)
+        a.waves_shift = g_knobs.digest_waves_shift;
+        hipLaunchKernelGGL(digest_kernel, dim3(lp.grid), dim3(lp.block), 0, stream, a);
+        return CEC_OK;
+    });
 }
 
 CEC_API int cec_digest(int n, const uint8_t *const *arenas, uint8_t *const *digests, const cec_plan *plan,
@@ -119,30 +104,28 @@ static int digest_limit(const char *op, uint64_t n_units, uint64_t *limit) {
 // checked to hold every tile's unit.  One wave per tile, four per workgroup.
 static int digest_update_launch(int dev, const Code &code, int lid_self, const uint8_t *diffs, uint8_t *digests,
                                 const TileSource &src, hipStream_t stream) {
-    if (src.n_tiles > kDigestMaxWork)
+    Launch l;
+    l.plan = plan_digest_update(src.n_tiles);
+    if (l.plan.refusal == kPlanTooLarge)
         return fail(CEC_EINVAL, "digest update: %llu tiles, one launch holds %llu",
                     static_cast<unsigned long long>(src.n_tiles), static_cast<unsigned long long>(kDigestMaxWork));
-    if (int rc = launch_countdown()) return rc;
-    std::vector<Pattern> pats(1, blank_pattern());
-    pats[0].n_in = code.k;
-    pats[0].n_out = 1;
-    for (int j = 0; j < code.k; ++j) set_coef(pats[0], 0, j, code.at(lid_self, j), CEC_ENGINE_PERM);
-    PatEntry *entry = nullptr;
-    if (int rc = pattern_tables(dev, pats, {}, stream, &entry)) return rc;
-    DigestUpdateArgs a;
-    memset(&a, 0, sizeof a);
-    a.diffs = diffs;
-    a.digests = digests;
-    a.tiles = src.tiles;
-    a.pattern = reinterpret_cast<const Pattern *>(entry->d);
-    a.n_tiles = static_cast<uint32_t>(src.n_tiles);
-    const uint32_t grid = static_cast<uint32_t>((src.n_tiles + 3) / 4);
-    hipLaunchKernelGGL(digest_update_kernel, dim3(grid), dim3(kBlock), 0, stream, a);
-    if (src.uses) src.uses->note(stream);
-    pattern_done(entry);
-    HIP_TRY(hipGetLastError());
-    record_launch(CEC_KERNEL_DIGEST_UPDATE, {1, 0}, kAccAll, false, 0, 0, grid, src.n_tiles, 0);
-    return CEC_OK;
+    Pattern pat = blank_pattern();
+    pat.n_in = code.k;
+    pat.n_out = 1;
+    for (int j = 0; j < code.k; ++j) set_coef(pat, 0, j, code.at(lid_self, j), CEC_ENGINE_PERM);
+    l.tb = Tables{nullptr, 1, &pat, nullptr};
+    l.uses[0] = src.uses;
+    return enqueue_launch(dev, stream, l, [&](const LaunchPlan &lp, const uint8_t *d) {
+        DigestUpdateArgs a;
+        memset(&a, 0, sizeof a);
+        a.diffs = diffs;
+        a.digests = digests;
+        a.tiles = src.tiles;
+        a.pattern = reinterpret_cast<const Pattern *>(d);
+        a.n_tiles = static_cast<uint32_t>(src.n_tiles);
+        hipLaunchKernelGGL(digest_update_kernel, dim3(lp.grid), dim3(lp.block), 0, stream, a);
+        return CEC_OK;
+    });
 }
 
 CEC_API int cec_digest_apply_diffs(int k, int m, const int *matrix, int lid_self, const uint8_t *diffs,
@@ -173,26 +156,26 @@ CEC_API int cec_digest_apply_diffs(int k, int m, const int *matrix, int lid_self
 static int digest_check_launch(int dev, cec_scrub_report *s, int k, int m, const int *matrix,
                                const uint8_t *const *data, const uint8_t *const *parity, int p0, int lt,
                                const TileSource &src, hipStream_t stream) {
-    if (int rc = launch_countdown()) return rc;
     const std::vector<Pattern> pats = scrub_patterns(Code{k, m, matrix}, p0, lt);
     DigestCheckArgs a;
     memset(&a, 0, sizeof a);
-    for (int j = 0; j < k; ++j) a.dig[j] = data[j];
-    for (int l = 0; l < lt; ++l) a.dig[k + l] = parity[p0 + l];
-    PatEntry *entry = nullptr;
-    if (int rc = pattern_tables(dev, pats, {}, stream, &entry)) return rc;
-    a.pattern = reinterpret_cast<const Pattern *>(entry->d);
+    for (int i = 0; i < k + lt; ++i) a.dig[i] = i < k ? data[i] : parity[p0 + i - k];
     a.words = s->d_buf + kScrubHead;
     a.counter = s->d_buf;
     a.n_units = static_cast<uint32_t>(src.n_tiles);  // (<= the report's max_tiles <= kScrubMaxTiles)
     a.syn_shift = static_cast<uint32_t>(p0);
-    const uint32_t grid = (a.n_units + kBlock - 1) / kBlock;
-    const Capacity cap = launch_digest_check(k, lt, a, grid, stream);
-    s->uses.note(stream);
-    pattern_done(entry);
-    HIP_TRY(hipGetLastError());
-    record_launch(CEC_KERNEL_DIGEST_CHECK, cap, kAccAll, false, 0, 0, grid, src.n_tiles, 0);
-    return CEC_OK;
+    Launch l;
+    l.plan = plan_digest_check(k, lt, src.n_tiles);
+    l.tb = Tables{nullptr, pats.size(), pats.data(), nullptr};
+    l.bases = a.dig;
+    l.en = k;
+    l.el = lt;
+    l.uses[0] = &s->uses;
+    return enqueue_launch(dev, stream, l, [&](const LaunchPlan &lp, const uint8_t *d) {
+        a.pattern = reinterpret_cast<const Pattern *>(d);
+        launch_digest_check(a, lp, stream);
+        return CEC_OK;
+    });
 }
 
 CEC_API int cec_scrub_digests(cec_scrub_report *s, int k, int m, const int *matrix,

@@ -484,10 +484,9 @@ static int pool_flush(cec_recovery_pool *p, uint8_t *const *out, bool to_host, v
         // (the pool's tile buffer: whole 4 KiB units on 4 KiB offsets)
         if (int rc = launch_combine(dev, fs.st,
                                     Tables{p->tables.d.get(), p->tables.cap_pats, p->tables.pats.data(), &used},
-                                    launch_shape(p->tables.pats, &used), engine == CEC_ENGINE_LDS,
-                                    TileSource::whole_units(p->tiles.alias<Tile>(), nt), s))
+                                    nullptr, launch_shape(p->tables.pats, &used), engine == CEC_ENGINE_LDS,
+                                    TileSource::whole_units(p->tiles.alias<Tile>(), nt), s, false))
             return rc;
-        HIP_TRY(hipGetLastError());
         // tile buffer and staging reusable; rebuilt shards visible if out is host memory
         if (int rc = stream_wait(s, to_host || (out && any_host_memory(out, k)))) return rc;
     }

@@ -30,6 +30,7 @@
 #include "../../include/reed_sol.h"
 #include "cec_hostplan.hpp"
 #include "cec_kernels.hpp"
+#include "cec_launchplan.hpp"
 #include "cec_poolbook.hpp"
 #include "gf256.hpp"
 
@@ -158,16 +159,16 @@ static void assign_rows(Pattern &p, std::vector<uint8_t> &rows) {
 }
 
 // ============================================================== launch
-// `lds`: dynamic LDS bytes of the launch (LDS engine: the largest pattern's rows).
+// The template dispatch of a planned launch (cec_launchplan.hpp): grid, workgroup size and
+// dynamic LDS are the plan's.
 template <int NT, int LT, class Eng, int kAcc, bool kExact, int S = kMaxStreams, bool kSysRel = false>
-static void launch_k(const CombineArgsN<S> &a, int grid, size_t lds, hipStream_t s) {
-    hipLaunchKernelGGL((combine_kernel<NT, LT, Eng, kAcc, kExact, S, kSysRel>), dim3(grid),
-                       dim3(kBlock >> a.split_shift), lds, s, a);
+static void launch_k(const CombineArgsN<S> &a, const LaunchPlan &lp, hipStream_t s) {
+    hipLaunchKernelGGL((combine_kernel<NT, LT, Eng, kAcc, kExact, S, kSysRel>), dim3(lp.grid), dim3(lp.block),
+                       lp.lds_bytes, s, a);
 }
 
 // The 1 x 1 shapes (region multiply-XOR / write, parity apply) with the two-slot
-// arguments, for launches whose patterns use slots 0 and 1 only.  narrow_args builds the
-// argument block they are passed (the launch-time check reads the same block).
+// arguments, for launches whose patterns use slots 0 and 1 only.
 static CombineArgsN<kNarrowStreams> narrow_args(const CombineArgs &w) {
     CombineArgsN<kNarrowStreams> a;
     memset(&a, 0, sizeof a);
@@ -184,133 +185,43 @@ static CombineArgsN<kNarrowStreams> narrow_args(const CombineArgs &w) {
 }
 
 template <class Eng>
-static bool launch_narrow(int acc, const CombineArgsN<kNarrowStreams> &a, int grid, size_t lds, hipStream_t s) {
+static bool launch_narrow(const CombineArgsN<kNarrowStreams> &a, const LaunchPlan &lp, hipStream_t s) {
     const bool rel = (a.flags & kFlagSysRelease) != 0;
-    if (acc == kAccAll && rel) launch_k<1, 1, Eng, kAccAll, true, kNarrowStreams, true>(a, grid, lds, s);
-    else if (acc == kAccAll) launch_k<1, 1, Eng, kAccAll, true, kNarrowStreams>(a, grid, lds, s);
-    else if (acc == kAccNone && rel) launch_k<1, 1, Eng, kAccNone, true, kNarrowStreams, true>(a, grid, lds, s);
-    else if (acc == kAccNone) launch_k<1, 1, Eng, kAccNone, true, kNarrowStreams>(a, grid, lds, s);
+    if (lp.acc == kAccAll && rel) launch_k<1, 1, Eng, kAccAll, true, kNarrowStreams, true>(a, lp, s);
+    else if (lp.acc == kAccAll) launch_k<1, 1, Eng, kAccAll, true, kNarrowStreams>(a, lp, s);
+    else if (lp.acc == kAccNone && rel) launch_k<1, 1, Eng, kAccNone, true, kNarrowStreams, true>(a, lp, s);
+    else if (lp.acc == kAccNone) launch_k<1, 1, Eng, kAccNone, true, kNarrowStreams>(a, lp, s);
     else return false;
     return true;
 }
 
-// The exact shapes (n_in, n_out, acc), X(N, L, A) for each -- the one list launch_exact's
-// kernels and has_exact are both made from: encode / decode / residual / solve (no RMW,
-// up to 8 inputs x 4 outputs), parity apply and region multiply-XOR (1 x 1 RMW),
-// diff-update (2 inputs, M parity RMW outputs, optionally + install).
-#define CEC_EXACT_WRITES(X, N) X(N, 1, kAccNone) X(N, 2, kAccNone) X(N, 3, kAccNone) X(N, 4, kAccNone)
-#define CEC_EXACT_SHAPES(X)                                                                      \
-    CEC_EXACT_WRITES(X, 1) CEC_EXACT_WRITES(X, 2) CEC_EXACT_WRITES(X, 3) CEC_EXACT_WRITES(X, 4)  \
-    CEC_EXACT_WRITES(X, 5) CEC_EXACT_WRITES(X, 6) CEC_EXACT_WRITES(X, 7) CEC_EXACT_WRITES(X, 8)  \
-    X(1, 1, kAccAll) X(2, 1, kAccAll) X(2, 2, kAccAll) X(2, 3, kAccAll) X(2, 4, kAccAll)         \
-    X(2, 2, kAccAllButLast) X(2, 3, kAccAllButLast) X(2, 4, kAccAllButLast)
-
+// One kernel per exact shape of CEC_EXACT_SHAPES, the list has_exact is made from.
 template <class Eng>
-static bool launch_exact(int n, int l, int acc, const CombineArgs &a, int grid, size_t lds,
-                         hipStream_t s) {
-#define CEC_X(N, L, A)                                           \
-    if (n == N && l == L && acc == A) {                          \
-        launch_k<N, L, Eng, A, true>(a, grid, lds, s);       \
-        return true;                                             \
+static bool launch_exact(const CombineArgs &a, const LaunchPlan &lp, hipStream_t s) {
+#define CEC_X(N, L, A)                                    \
+    if (lp.nt == N && lp.lt == L && lp.acc == A) {        \
+        launch_k<N, L, Eng, A, true>(a, lp, s);           \
+        return true;                                      \
     }
     CEC_EXACT_SHAPES(CEC_X)
 #undef CEC_X
     return false;
 }
 
-static bool has_exact(int n, int l, int acc) {
-#define CEC_X(N, L, A) if (n == N && l == L && acc == A) return true;
-    CEC_EXACT_SHAPES(CEC_X)
-#undef CEC_X
-    return false;
-}
-
-// The capacity ladder: a launch of nt inputs and lt outputs that has no exact kernel runs
-// the capacity kernel of the next rung up, inputs 2 / 4 / 8 / 16 (the scrub kernels start
-// at 4) and outputs 1 / 2 / 4.  CEC_CAPACITY_RUNGS(nt, lt, K) runs K(NT, LT) for that rung;
-// K launches its kernel template and returns the Capacity (the launch record's nt / lt).
-struct Capacity {
-    int nt, lt;
-};
-#define CEC_LT_RUNGS(lt, NT, K)                  \
-    if (lt <= 1) { K(NT, 1) }                    \
-    else if (lt <= 2) { K(NT, 2) }               \
-    else { K(NT, 4) }
-#define CEC_CAPACITY_RUNGS_FROM_4(nt, lt, K)     \
-    if (nt <= 4) { CEC_LT_RUNGS(lt, 4, K) }      \
-    else if (nt <= 8) { CEC_LT_RUNGS(lt, 8, K) } \
-    else { CEC_LT_RUNGS(lt, 16, K) }
-#define CEC_CAPACITY_RUNGS(nt, lt, K)            \
-    if (nt <= 2) { CEC_LT_RUNGS(lt, 2, K) }      \
-    else { CEC_CAPACITY_RUNGS_FROM_4(nt, lt, K) }
-
-// Capacity kernels for every shape without an exact one (guarded, per-pattern counts and modes).
+// Capacity kernels for every shape without an exact one (guarded, per-pattern counts and
+// modes): the plan's rung of the capacity ladder.
 template <class Eng>
-static Capacity launch_generic(int nt, int lt, const CombineArgs &a, int grid, size_t lds, hipStream_t s) {
-#define CEC_G(NT, LT)                                              \
-    launch_k<NT, LT, Eng, kAccRuntime, false>(a, grid, lds, s);   \
-    return {NT, LT};
-    CEC_CAPACITY_RUNGS(nt, lt, CEC_G)
+static void launch_generic(const CombineArgs &a, const LaunchPlan &lp, hipStream_t s) {
+#define CEC_G(NT, LT)                                       \
+    launch_k<NT, LT, Eng, kAccRuntime, false>(a, lp, s);    \
+    return;
+    CEC_CAPACITY_RUNGS(lp.nt, lp.lt, CEC_G)
 #undef CEC_G
-}
-
-// Shape class of the patterns a launch uses (`used`: pattern indices its tiles name;
-// NULL = all): exact (n_in, n_out, acc) if they all agree.
-static bool exact_shape(const std::vector<Pattern> &pats, const std::vector<char> *used, int *n, int *l,
-                        int *acc) {
-    const Pattern *p0 = nullptr;
-    for (size_t i = 0; i < pats.size(); ++i) {
-        if (used && !(*used)[i]) continue;
-        const Pattern &p = pats[i];
-        if (!p0) {
-            p0 = &p;
-            continue;
-        }
-        if (p.n_in != p0->n_in || p.n_out != p0->n_out) return false;
-        for (int o = 0; o < p.n_out; ++o)
-            if (p.out_mode[o] != p0->out_mode[o]) return false;
-    }
-    if (!p0) return false;
-    int nx = 0;
-    for (int o = 0; o < p0->n_out; ++o) nx += p0->out_mode[o] == kModeXor;
-    if (nx == 0) *acc = kAccNone;
-    else if (nx == p0->n_out) *acc = kAccAll;
-    else if (nx == p0->n_out - 1 && p0->out_mode[p0->n_out - 1] == kModeWrite) *acc = kAccAllButLast;
-    else return false;
-    *n = p0->n_in;
-    *l = p0->n_out;
-    return true;
 }
 
 #include "cec_combo.inc"
 
 // ============================================================== plans
-// Tiles of one extent end on 4 KiB boundaries of the arena offset, so interior
-// tiles cover whole 128-B lines and only an extent's first / last tile shares a line
-// with a neighbouring workgroup (ecalloc packs values at 16-B granularity; tiling
-// from each value's start measured 4 % slower on the mixed workload).
-static inline size_t tiles_of(uint64_t off, uint32_t len) {
-    return len ? static_cast<size_t>((off % kTile + len + kTile - 1) / kTile) : 0;
-}
-static inline size_t append_tiles(Tile *t, uint64_t off, uint64_t src_off, uint32_t len,
-                                  uint32_t pattern) {
-    size_t n = 0;
-    for (uint32_t o = 0; o < len;) {
-        const uint32_t phase = static_cast<uint32_t>((off + o) % kTile);
-        const uint32_t step = std::min<uint32_t>(kTile - phase, len - o);
-        t[n++] = Tile{off + o, src_off + o, step, pattern};
-        o += step;
-    }
-    return n;
-}
-// Full tiles whose arena offset sits on a 128-B line (the written side: a line
-// written by two workgroups costs more than one read by two).
-static inline int64_t count_line_tiles(const Tile *t, size_t n) {
-    int64_t c = 0;
-    for (size_t i = 0; i < n; ++i) c += t[i].len == kTile && (t[i].off & (kLineBytes - 1)) == 0;
-    return c;
-}
-
 struct cec_plan {
     int device = -1;
     int n_ext = 0;
@@ -473,165 +384,39 @@ struct WaveTiles {
     }
 };
 
-// Workgroups per tile (log2).  Full tiles on 128-B lines stream fastest as four
-// 64-lane workgroups (finer dispatch, every wave equal work).  A launch that is mostly
-// small or line-misaligned tiles keeps one 256-lane workgroup per tile: splitting
-// those multiplies empty workgroups and partial lines written by two workgroups
-// (measured: DESIGN.md section 4).  CEC_SPLIT_SHIFT=0..2 pins the choice.
-static uint32_t split_shift_for(const Streams &st, const TileSource &src) {
-    static const int forced = [] {
-        const char *e = getenv("CEC_SPLIT_SHIFT");
-        return e && *e ? std::min(2, std::max(0, atoi(e))) : -1;
-    }();
-    if (forced >= 0) return static_cast<uint32_t>(forced);
-    uintptr_t mis = 0;
-    for (int i = 0; i < kMaxStreams; ++i) mis |= reinterpret_cast<uintptr_t>(st.base[i]);
-    const bool full = src.n_line_tiles * 4 >= src.n_tiles * 3;
-    return full && (mis & (kLineBytes - 1)) == 0 ? 2u : 0u;
-}
+// The measurement overrides in force (cec_launchplan.hpp), read from the environment once.
+static const Knobs g_knobs = Knobs::from_env();
 
-// Waves per CU a launch may hold (0 = as many as fit).  Fewer streaming waves per CU
-// keep fewer HBM requests in flight; the cap is applied by sizing each workgroup's
-// dynamic LDS so that only cap / (waves per workgroup) workgroups fit on a CU.
-// CEC_WAVES_PER_CU overrides it (measurement).
+// The occupancy cap (occupancy_lds).  CEC_WAVES_PER_CU overrides it (measurement).
 static std::atomic<int> g_waves_per_cu{[] {
     const char *e = getenv("CEC_WAVES_PER_CU");
     return e && *e ? std::max(0, atoi(e)) : 0;
 }()};
 static int waves_per_cu_cap() { return g_waves_per_cu.load(std::memory_order_relaxed); }
 
-static size_t occupancy_lds(int dev, uint32_t split_shift) {
-    const int cap = waves_per_cu_cap();
-    if (cap <= 0) return 0;
-    const int waves_per_wg = (kBlock >> split_shift) / 64;
-    const int wgs = std::max(1, cap / std::max(1, waves_per_wg));
-    const size_t per_cu = g_dev[dev].lds_per_cu;
-    const size_t lds = per_cu / static_cast<size_t>(wgs);
-    return std::min<size_t>(65536, lds > 256 ? lds - 256 : 0);  // strictly below the boundary
-}
-
-// Store policy of a launch (kFlagWriteThrough).  Write-through (sc1) stores finish the
-// launches of up to 512 MiB of streamed bytes sooner, non-temporal stores the larger
-// ones.  RS(3,2) 4 KiB step, bench.py's strong-scaling shares, 3 processes per policy on
-// one box (profiles/r03_evidence/store_policy_ab/): encode / decode us
-//   8,192 stripes   nt 29.9-31.7 / 23.6-23.9   wt 27.5-28.6 / 22.3-22.6
-//  16,384 stripes   nt 54.0-55.3 / 45.5-45.6   wt 53.4-54.0 / 41.0-41.6
-//  32,768 stripes   nt 105.9-106.2 / 88.1-88.6 wt 112.5-112.7 / 81.1-81.8
-//  65,536 stripes   nt 208.0-212.2 / 178.0-178.3  wt 223.3-224.8 / 184.8-186.1
-// i.e. write-through wins at <= 335 MB (encode) and <= 537 MB (decode) per launch and
-// loses at 671 MB (encode) and above.  Auto: write-through when the launch streams at
-// most g_wt_max_bytes (reads + writes).  CEC_STORE_POLICY=nt|wt|auto and
-// CEC_WT_MAX_BYTES override (measurement).
-enum { kStoreAuto = 0, kStoreNt = 1, kStoreWt = 2 };
-// An unknown value (e.g. "WT") is reported on stderr once and ignored (auto).
-static const int g_store_policy = [] {
-    const char *e = getenv("CEC_STORE_POLICY");
-    if (!e || !*e || !strcmp(e, "auto")) return static_cast<int>(kStoreAuto);
-    if (!strcmp(e, "wt")) return static_cast<int>(kStoreWt);
-    if (!strcmp(e, "nt")) return static_cast<int>(kStoreNt);
-    fprintf(stderr, "libcocytus_ec: CEC_STORE_POLICY=%s is not nt, wt or auto; using auto\n", e);
-    return static_cast<int>(kStoreAuto);
-}();
-// A byte count from the environment; a bad value is reported on stderr once and ignored.
-static uint64_t parse_byte_count(const char *name, uint64_t dflt) {
-    const char *e = getenv(name);
-    if (!e || !*e) return dflt;
-    // strtoull alone would take "-1" as 2^64 - 1 and skip leading blanks: a byte count is
-    // digits only (decimal, 0x hex or 0 octal), in range
-    char *end = nullptr;
-    errno = 0;
-    const unsigned long long v = (*e >= '0' && *e <= '9') ? strtoull(e, &end, 0) : 0;
-    if (!(*e >= '0' && *e <= '9') || !end || *end || errno == ERANGE) {
-        fprintf(stderr, "libcocytus_ec: %s=%s is not a byte count; using %llu\n", name, e,
-                static_cast<unsigned long long>(dflt));
-        return dflt;
-    }
-    return static_cast<uint64_t>(v);
-}
-static const uint64_t g_wt_max_bytes = parse_byte_count("CEC_WT_MAX_BYTES", uint64_t(512) << 20);
 // The store policy in force (tests: every kernel kind runs under each).
 CEC_API int cec_internal_store_policy(uint64_t *wt_max_bytes) {
-    if (wt_max_bytes) *wt_max_bytes = g_wt_max_bytes;
-    return g_store_policy;
+    if (wt_max_bytes) *wt_max_bytes = g_knobs.wt_max_bytes;
+    return g_knobs.store_policy;
 }
-// A launch too large for write-through keeps non-temporal stores for its body and writes
-// its last g_wt_tail_bytes (all outputs together) through.  Plain bench step (RS(3,2),
-// 65,536 x 4 KiB, encode + rotating decode), 3 interleaved processes per tail on one box,
-// GiB/s (profiles/store_tail_ab.md): no tail 2553-2581, 32 MiB 2568-2610, 64 MiB
-// 2600-2634, 96 MiB 2643-2659, 128 MiB 2651-2666, 144 MiB 2647-2653, 160 MiB 2605-2612,
-// 192 MiB 2520-2529, 256 MiB 2431-2449: a plateau from 96 to 144 MiB, the smallest of it
-// taken.  The launch boundary is the same 5 us with and without (tools/trace_check.py):
-// the gain is in the kernels' own time, the last writes of a launch being taken up on
-// the memory side.  CEC_WT_TAIL_BYTES overrides (measurement); 0: no tail.
-static const uint64_t g_wt_tail_bytes = parse_byte_count("CEC_WT_TAIL_BYTES", uint64_t(96) << 20);
-
-// Which work items of a launch store write-through: all (the kFlagWriteThrough launch),
-// none, or those from `from` on.  `streamed`: the bytes the launch reads and writes.
-struct StoreChoice {
-    bool all;
-    uint64_t from;  // kNoWtTail: none
-};
-static StoreChoice write_through(uint64_t n_tiles, uint32_t split_shift, int lt, uint64_t streamed) {
-    if (g_store_policy != kStoreAuto) return {g_store_policy == kStoreWt, kNoWtTail};
-    if (streamed <= g_wt_max_bytes) return {true, kNoWtTail};
-    if (g_wt_tail_bytes == 0 || lt <= 0) return {false, kNoWtTail};
-    const uint64_t per_item = static_cast<uint64_t>(lt) * (kTile >> split_shift);  // bytes one work item writes
-    const uint64_t items = g_wt_tail_bytes / per_item + (g_wt_tail_bytes % per_item != 0);
-    const uint64_t n_work = n_tiles << split_shift;
-    if (items >= n_work) return {true, kNoWtTail};  // the tail is the whole launch
-    return {false, n_work - items};
-}
-// Test hook: the choice for a launch of n_tiles tiles, lt outputs, `streamed` bytes.
-// Returns 0 none, 1 a tail from *wt_from, 2 all.
+// Test hook: write_through's choice for a launch of n_tiles tiles, lt outputs, `streamed`
+// bytes.  Returns 0 none, 1 a tail from *wt_from, 2 all.
 CEC_API int cec_internal_wt_from(uint64_t n_tiles, uint32_t split_shift, int lt, uint64_t streamed,
                                  uint64_t *wt_tail_bytes, uint64_t *wt_from) {
     if (split_shift > 2 || n_tiles > 0xFFFFFFFFull) return fail(CEC_EINVAL, "cec_internal_wt_from: bad args");
-    const StoreChoice c = write_through(n_tiles, split_shift, lt, streamed);
-    if (wt_tail_bytes) *wt_tail_bytes = g_wt_tail_bytes;
+    const StoreChoice c = write_through(g_knobs, n_tiles, split_shift, lt, streamed);
+    if (wt_tail_bytes) *wt_tail_bytes = g_knobs.wt_tail_bytes;
     if (wt_from) *wt_from = c.from;
     return c.all ? 2 : c.from != kNoWtTail ? 1 : 0;
 }
 
-// The kernel a pattern set takes: capacities, LDS rows, and the exact shape if every
-// pattern the launch uses has the same one.
-struct LaunchShape {
-    int nt = 1, lt = 0, max_rows = 0;
-    bool exact = false;
-    int en = 0, el = 0, eacc = 0;
-    int streams = 0;  // 1 + the highest stream slot a used pattern names
-};
-
-static LaunchShape launch_shape(const std::vector<Pattern> &pats, const std::vector<char> *used) {
-    LaunchShape sh;
-    for (size_t i = 0; i < pats.size(); ++i) {
-        if (used && !(*used)[i]) continue;
-        sh.nt = std::max(sh.nt, pats[i].n_in);
-        sh.lt = std::max(sh.lt, pats[i].n_out);
-        sh.max_rows = std::max(sh.max_rows, pats[i].lds_rows);
-        for (int j = 0; j < pats[i].n_in; ++j) sh.streams = std::max(sh.streams, pats[i].in_stream[j] + 1);
-        for (int j = 0; j < pats[i].n_out; ++j) sh.streams = std::max(sh.streams, pats[i].out_stream[j] + 1);
-    }
-    sh.exact = exact_shape(pats, used, &sh.en, &sh.el, &sh.eacc);
-    return sh;
-}
-
-enum KernelKind { kKindNarrow, kKindExact, kKindGeneric };
-static_assert(kKindNarrow == CEC_KERNEL_NARROW && kKindExact == CEC_KERNEL_EXACT &&
-                  kKindGeneric == CEC_KERNEL_GENERIC, "cec_launch_record::kind");
-static_assert(kAccNone == CEC_ACC_NONE && kAccAll == CEC_ACC_ALL && kAccAllButLast == CEC_ACC_ALL_BUT_LAST &&
-                  kAccRuntime == CEC_ACC_RUNTIME, "cec_launch_record::acc");
-static_assert(kFlagSysRelease == CEC_LAUNCH_SYS_RELEASE && kFlagWriteThrough == CEC_LAUNCH_WRITE_THROUGH &&
-                  kFlagWtTail == CEC_LAUNCH_WT_TAIL, "cec_launch_record::flags");
-
 // The calling thread's last enqueued kernel launch (cec_last_launch).  record_launch is
-// the one place that writes it: launch_combine, scrub_launch and the three digest launches
-// (cec_digest.inc), the library's launch routines, each call it once per kernel they enqueue.
+// the one place that writes it, and enqueue_launch its one caller.
 static thread_local cec_launch_record t_last_launch = {0, -1, 0, 0, -1, -1, 0, 0, 0, 0, 0, kNoWtTail};
 
-static void record_launch(int kind, Capacity cap, int acc, bool lds, uint32_t split_shift, uint32_t flags,
-                          uint32_t grid, uint64_t n_tiles, size_t lds_bytes, uint64_t wt_from = kNoWtTail) {
-    t_last_launch = {t_last_launch.seq + 1, kind, cap.nt, cap.lt, acc, lds ? CEC_ENGINE_LDS : CEC_ENGINE_PERM,
-                     split_shift, flags, grid, n_tiles, lds_bytes, wt_from};
+static void record_launch(const LaunchPlan &lp) {
+    t_last_launch = {t_last_launch.seq + 1, lp.kind, lp.nt, lp.lt, lp.acc, lp.engine, lp.split_shift, lp.flags,
+                     lp.grid, lp.n_tiles, lp.lds_bytes, lp.wt_from};
 }
 
 CEC_API int cec_last_launch(cec_launch_record *out) {
@@ -642,8 +427,8 @@ CEC_API int cec_last_launch(cec_launch_record *out) {
 
 // Test hook (cec_internal_fail_launch): the calling thread's next `after` launches run, the
 // one after them is refused as a HIP failure, then the hook disarms.  -1: off.
-// Counted by run_combine, scrub_launch and the digest launches (launch_countdown), before
-// anything is built.
+// Counted by enqueue_launch (launch_countdown) for run_combine, scrub_launch and the digest
+// launches, before anything is pinned.
 static thread_local int t_fail_after = -1;
 CEC_API int cec_internal_fail_launch(int after) {
     t_fail_after = after < 0 ? -1 : after;
@@ -659,137 +444,130 @@ static int launch_countdown() {
 }
 
 // The device copy of a pattern set from the coefficient cache, for a launch on stream s:
-// patterns and the LDS engine's product rows are one blob, rows after the patterns (16-B
-// aligned: sizeof(Pattern) is a multiple of 16), and the blob's bytes are its cache key.
-// *entry is pinned against eviction until pattern_done, which the caller calls once its
-// launch is enqueued (eviction synchronises the device).
-static int pattern_tables(int dev, const std::vector<Pattern> &pats, const std::vector<uint8_t> &rows,
+// patterns and the LDS engine's product rows (NULL: none) are one blob, rows after the
+// patterns (16-B aligned: sizeof(Pattern) is a multiple of 16), and the blob's bytes are its
+// cache key.  *entry is pinned against eviction until pattern_done, which the caller calls
+// once its launch is enqueued (eviction synchronises the device).
+static int pattern_tables(int dev, const Pattern *pats, size_t n_pats, const std::vector<uint8_t> *rows,
                           hipStream_t s, PatEntry **entry) {
-    std::string key(reinterpret_cast<const char *>(pats.data()), pats.size() * sizeof(Pattern));
-    key.append(reinterpret_cast<const char *>(rows.data()), rows.size());
+    std::string key(reinterpret_cast<const char *>(pats), n_pats * sizeof(Pattern));
+    if (rows) key.append(reinterpret_cast<const char *>(rows->data()), rows->size());
     return pattern_get(dev, std::move(key), s, entry);
 }
 
-// The pattern set of one launch: where it lies on the device, and its host copy for the
-// launch-time stream check.
-struct Tables {
-    const uint8_t *d;               // device blob: n_pats patterns, then the LDS engine's rows
-    size_t n_pats;
-    const Pattern *host;            // the same patterns on the host
-    const std::vector<char> *used;  // which of them the launch's tiles name (NULL: all)
+// What a launch path hands enqueue_launch: the plan its planner made (cec_launchplan.hpp)
+// and what the sequence around the dispatch needs.
+struct Launch {
+    LaunchPlan plan;
+    bool counted = true;  // by the fail hook (not the region multiply, nor the pool's flush)
+    Tables tb{};          // the kernel's patterns (n_pats == 0: it has none); d == NULL: pinned
+                          // here for the length of the enqueue, with `rows` behind them
+    const std::vector<uint8_t> *rows = nullptr;
+    const uint8_t *const *bases = nullptr;  // the argument block's streams, for the layout check
+                                            // (NULL: the kernel's patterns name none by slot)
+    int en = 0, el = 0;                     // the exact shape, for the refusal's message
+    Tracker *uses[2] = {nullptr, nullptr};  // whose destroy waits for the launch's stream
 };
 
-// Launch-time check of the argument block a kernel is passed: every stream slot a used
-// pattern names must be one the block carries (below 2 for the narrow kernels, whose
-// block is narrow_args' copy of the first two slots; below kMaxStreams otherwise) and
-// hold a non-NULL base there.  Which arena the op meant for each slot is decided by the
-// op itself (it fills the slots); this check catches a kernel choice or an argument block
-// that cannot serve the patterns -- a slot the kernel's block does not have, or an empty
-// one -- which would otherwise fault the GPU.  A failure is refused.
-static bool stream_layout_ok(const uint8_t *const *bases, int slots, const Tables &tb) {
-    for (size_t q = 0; q < tb.n_pats; ++q) {
-        if (tb.used && (q >= tb.used->size() || !(*tb.used)[q])) continue;
-        const Pattern &p = tb.host[q];
-        for (int i = 0; i < p.n_in; ++i)
-            if (p.in_stream[i] >= slots || !bases[p.in_stream[i]]) return false;
-        for (int l = 0; l < p.n_out; ++l)
-            if (p.out_stream[l] >= slots || !bases[p.out_stream[l]]) return false;
+static int plan_refused(const Launch &l) {
+    const LaunchPlan &lp = l.plan;
+    switch (lp.refusal) {
+    case kPlanStreams:
+        return fail(CEC_EINVAL, "internal: an op names more than %d byte streams; not launched", kMaxStreams);
+    case kPlanLayout:
+        return fail(CEC_EINVAL, "internal: a launch's argument block cannot serve its patterns "
+                                "(kind %d, %d x %d); not launched", lp.kind, l.en, l.el);
+    default:  // (the ops refuse these in their own words before they enqueue)
+        return fail(CEC_EINVAL, "internal: kernel kind %d cannot run %llu tiles of %d x %d in one launch; not launched",
+                    lp.kind, static_cast<unsigned long long>(lp.n_tiles), l.en, l.el);
     }
-    return true;
 }
 
-// `narrow`: the block a narrow kernel is passed (NULL: the launch passes `a` itself).
-static bool layout_ok_for(const CombineArgs &a, const CombineArgsN<kNarrowStreams> *narrow, const Tables &tb) {
-    return narrow ? stream_layout_ok(narrow->base, kNarrowStreams, tb) : stream_layout_ok(a.base, kMaxStreams, tb);
+// The one enqueue sequence of the library, for every kernel with a launch record: the fail
+// hook's countdown, the tables pinned, the layout check, `dispatch(plan, tables)` -- the
+// path's own argument block and template dispatch --, the streams noted, the tables
+// unpinned on every exit, hipGetLastError, the record.
+template <class Dispatch>
+static int enqueue_launch(int dev, hipStream_t stream, Launch &l, Dispatch &&dispatch) {
+    if (l.counted)
+        if (int r = launch_countdown()) return r;
+    if (l.plan.refusal == kPlanNothing) return CEC_OK;
+    PatEntry *entry = nullptr;
+    if (l.plan.refusal == kPlanOk && l.tb.n_pats && !l.tb.d) {
+        if (int r = pattern_tables(dev, l.tb.host, l.tb.n_pats, l.rows, stream, &entry)) return r;
+        l.tb.d = entry->d;
+    }
+    if (l.bases) check_layout(l.plan, l.bases, l.tb);
+    const int rc = l.plan.refusal == kPlanOk ? dispatch(l.plan, l.tb.d) : plan_refused(l);
+    for (Tracker *u : l.uses)
+        if (u) u->note(stream);  // (host-side only)
+    if (entry) pattern_done(entry);
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    record_launch(l.plan);
+    return CEC_OK;
 }
 
-// One launch over the tiles of `src` (at least one) with the tables `tb` already on the
-// device, recorded for cec_last_launch.  The caller checks hipGetLastError.
+// One launch over the tiles of `src` with the patterns of `tb` (tb.d == NULL: pinned for the
+// launch, with `rows`), recorded for cec_last_launch.
 // *released: whether every wave of the launch ends with a system-scope release
 // (kFlagSysRelease asked for, and honoured: only the narrow 1 x 1 launches carry it).
-static int launch_combine(int dev, const Streams &st, const Tables &tb, const LaunchShape &sh, bool lds,
-                          const TileSource &src, hipStream_t stream, uint32_t flags = 0, bool *released = nullptr) {
-    if (st.refused) return fail(CEC_EINVAL, "internal: an op names more than %d byte streams; not launched", kMaxStreams);
-    CombineArgs a;
-    memset(&a, 0, sizeof a);
-    a.flags = flags;
-    // Which kernel runs: the exact-shape one if the shape has an instantiation, the narrow
-    // two-slot one for 1 x 1 launches over slots 0 and 1, else a capacity kernel.
-    const bool exact_k = sh.exact && has_exact(sh.en, sh.el, sh.eacc);
-    const KernelKind kind =
-        exact_k && sh.en == 1 && sh.el == 1 && sh.streams <= kNarrowStreams &&
-                (sh.eacc == kAccAll || sh.eacc == kAccNone)
-            ? kKindNarrow
-            : exact_k ? kKindExact : kKindGeneric;
-    for (int i = 0; i < kMaxStreams; ++i) a.base[i] = st.base[i];
-    a.tiles = src.tiles;
-    a.implicit_len = src.implicit_len;
-    a.patterns = reinterpret_cast<const Pattern *>(tb.d);
-    a.rows = tb.d + tb.n_pats * sizeof(Pattern);
-    a.n_tiles = static_cast<uint32_t>(src.n_tiles);
-    // One workgroup per (part of a) tile, dispatched in tile order, so the set of
-    // tiles in flight is a contiguous window of the arenas (measured 5-12 % over a
-    // persistent grid-stride grid: DESIGN.md).  The LDS engine stages its pattern's
-    // product rows per workgroup (512 B for an RS(3,2) encode, from L2).
-    a.split_shift = split_shift_for(st, src);
-    // The store policy.  A tail needs the full block's wt_from and the PERM engine's store
-    // branch: the narrow and the LDS engine's kernels have neither, and get no tail.
-    const StoreChoice wt = write_through(src.n_tiles, a.split_shift, sh.lt,
-                                         src.n_tiles * kTile * static_cast<uint64_t>(sh.nt + sh.lt));
-    a.wt_from = kind == kKindNarrow || lds ? kNoWtTail : wt.from;
-    a.flags |= (wt.all ? kFlagWriteThrough : 0u) | (a.wt_from != kNoWtTail ? kFlagWtTail : 0u);
-    const size_t lds_bytes = std::max(lds ? static_cast<size_t>(sh.max_rows) * 256 : 0,
-                                      occupancy_lds(dev, a.split_shift));
-    // A dispatch holds at most 2^32 - 1 work items per dimension: past that (more than
-    // 64 GiB of tiles per stream) workgroups walk the rest grid-stride.
-    const uint64_t max_wgs = 0xFFFFFFFFull / (kBlock >> a.split_shift);
-    const int grid = static_cast<int>(std::min<uint64_t>(src.n_tiles << a.split_shift, max_wgs));
-    a.grid = static_cast<uint32_t>(grid);
-    CombineArgsN<kNarrowStreams> na;  // the narrow kernels' block: checked and passed
-    if (kind == kKindNarrow) na = narrow_args(a);
-    if (!layout_ok_for(a, kind == kKindNarrow ? &na : nullptr, tb))
-        return fail(CEC_EINVAL, "internal: a launch's argument block cannot serve its patterns "
-                                "(kind %d, %d x %d); not launched", static_cast<int>(kind), sh.en, sh.el);
-    bool ok;
-    Capacity cap = {sh.en, sh.el};  // exact and narrow kernels: the shape itself
-    if (kind == kKindNarrow) {
-        ok = lds ? launch_narrow<LdsEngine>(sh.eacc, na, grid, lds_bytes, stream)
-                 : launch_narrow<PermEngine>(sh.eacc, na, grid, lds_bytes, stream);
-    } else if (kind == kKindExact) {
-        ok = lds ? launch_exact<LdsEngine>(sh.en, sh.el, sh.eacc, a, grid, lds_bytes, stream)
-                 : launch_exact<PermEngine>(sh.en, sh.el, sh.eacc, a, grid, lds_bytes, stream);
-    } else {
-        cap = lds ? launch_generic<LdsEngine>(sh.nt, sh.lt, a, grid, lds_bytes, stream)
-                  : launch_generic<PermEngine>(sh.nt, sh.lt, a, grid, lds_bytes, stream);
-        ok = true;
-    }
-    if (!ok) return fail(CEC_EINVAL, "internal: no %s kernel for %d x %d", kind == kKindNarrow ? "narrow" : "exact",
-                         sh.en, sh.el);
-    if (released) *released = kind == kKindNarrow && (flags & kFlagSysRelease) != 0;
-    record_launch(kind, cap, kind == kKindGeneric ? static_cast<int>(kAccRuntime) : sh.eacc, lds, a.split_shift,
-                  a.flags, a.grid, src.n_tiles, lds_bytes, a.wt_from);
-    return CEC_OK;
+static int launch_combine(int dev, const Streams &st, const Tables &tb, const std::vector<uint8_t> *rows,
+                          const LaunchShape &sh, bool lds, const TileSource &src, hipStream_t stream, bool counted,
+                          uint32_t flags = 0, bool *released = nullptr) {
+    uintptr_t bases_or = 0;
+    for (int i = 0; i < kMaxStreams; ++i) bases_or |= reinterpret_cast<uintptr_t>(st.base[i]);
+    Launch l;
+    l.plan = plan_combine(sh, src.n_tiles, src.n_line_tiles, bases_or, lds, flags, g_knobs, waves_per_cu_cap(),
+                          g_dev[dev].lds_per_cu);
+    if (st.refused) l.plan.refusal = kPlanStreams;
+    l.counted = counted;
+    l.tb = tb;
+    l.rows = rows;
+    l.bases = st.base;
+    l.en = sh.en;
+    l.el = sh.el;
+    l.uses[0] = src.uses;  // a plan's streams, for its destroy
+    if (released) *released = l.plan.kind == kKindNarrow && (flags & kFlagSysRelease) != 0;
+    return enqueue_launch(dev, stream, l, [&](const LaunchPlan &lp, const uint8_t *d) {
+        CombineArgs a;
+        memset(&a, 0, sizeof a);
+        for (int i = 0; i < kMaxStreams; ++i) a.base[i] = st.base[i];
+        a.tiles = src.tiles;
+        a.implicit_len = src.implicit_len;
+        a.patterns = reinterpret_cast<const Pattern *>(d);
+        a.rows = d + tb.n_pats * sizeof(Pattern);
+        a.n_tiles = static_cast<uint32_t>(lp.n_tiles);
+        a.split_shift = lp.split_shift;
+        a.grid = lp.grid;
+        a.flags = lp.flags;
+        a.wt_from = lp.wt_from;
+        const bool perm = lp.engine == CEC_ENGINE_PERM;
+        bool ok = true;
+        if (lp.kind == kKindNarrow) {  // (the block the layout check saw: the first two slots)
+            const CombineArgsN<kNarrowStreams> na = narrow_args(a);
+            ok = perm ? launch_narrow<PermEngine>(na, lp, stream) : launch_narrow<LdsEngine>(na, lp, stream);
+        } else if (lp.kind == kKindExact) {
+            ok = perm ? launch_exact<PermEngine>(a, lp, stream) : launch_exact<LdsEngine>(a, lp, stream);
+        } else {
+            perm ? launch_generic<PermEngine>(a, lp, stream) : launch_generic<LdsEngine>(a, lp, stream);
+        }
+        return ok ? CEC_OK
+                  : fail(CEC_EINVAL, "internal: no %s kernel for %d x %d", lp.kind == kKindNarrow ? "narrow" : "exact",
+                         lp.nt, lp.lt);
+    });
 }
 
 // One launch over a tile source with a pattern set built for `engine` (the patterns'
 // coefficient form and the kernel must agree: the engine is read once per op, so a
-// concurrent cec_set_engine cannot split them).
+// concurrent cec_set_engine cannot split them).  Counted by the fail hook even where the
+// source is empty.
 static int run_combine(int dev, const Streams &st, const std::vector<Pattern> &pats,
                        const std::vector<uint8_t> &rows, const TileSource &src, hipStream_t stream,
                        const std::vector<char> *used, int engine) {
-    if (int r = launch_countdown()) return r;
-    if (src.n_tiles == 0 || pats.empty()) return CEC_OK;
-    const LaunchShape sh = launch_shape(pats, used);
-    if (sh.lt == 0) return CEC_OK;
-    PatEntry *entry = nullptr;
-    if (int r = pattern_tables(dev, pats, rows, stream, &entry)) return r;
-    const int rc = launch_combine(dev, st, Tables{entry->d, pats.size(), pats.data(), used}, sh,
-                                  engine == CEC_ENGINE_LDS, src, stream);
-    if (src.uses) src.uses->note(stream);  // a plan's streams, for its destroy (host-side only)
-    pattern_done(entry);
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return CEC_OK;
+    return launch_combine(dev, st, Tables{nullptr, pats.size(), pats.data(), used}, &rows,
+                          src.n_tiles ? launch_shape(pats, used) : LaunchShape{}, engine == CEC_ENGINE_LDS, src, stream,
+                          true);
 }
 
 // The patterns of launch g of a combo list: outputs [4g, 4g+4) of every combo, with the
@@ -924,7 +702,7 @@ CEC_API int cec_set_engine(cec_engine e) {
 CEC_API cec_engine cec_get_engine(void) { return static_cast<cec_engine>(g_engine.load()); }
 CEC_API int cec_last_engine(void) { return t_last_engine; }
 
-// Test hook: the launch-time check (layout_ok_for) on one pattern, as launch_combine
+// Test hook: the launch-time check (stream_layout_ok) on one pattern, as enqueue_launch
 // runs it, for a narrow or a full argument block built from `bases`.  Host only.
 CEC_API int cec_internal_check_launch_layout(int narrow, const int *in_slots, int n_in, const int *out_slots,
                                              int n_out, const void *const *bases, int n_bases) {
@@ -942,11 +720,9 @@ CEC_API int cec_internal_check_launch_layout(int narrow, const int *in_slots, in
         if (out_slots[l] < 0 || out_slots[l] >= kMaxStreams) return fail(CEC_EINVAL, "slot %d", out_slots[l]);
         p.out_stream[l] = static_cast<uint8_t>(out_slots[l]);
     }
-    CombineArgs a;
-    memset(&a, 0, sizeof a);
-    for (int i = 0; i < n_bases; ++i) a.base[i] = static_cast<uint8_t *>(const_cast<void *>(bases[i]));
-    const CombineArgsN<kNarrowStreams> na = narrow_args(a);
-    if (!layout_ok_for(a, narrow ? &na : nullptr, Tables{nullptr, 1, &p, nullptr}))
+    const uint8_t *block[kMaxStreams] = {};  // (a narrow block is the first two slots)
+    for (int i = 0; i < n_bases; ++i) block[i] = static_cast<const uint8_t *>(bases[i]);
+    if (!stream_layout_ok(block, narrow ? kNarrowStreams : kMaxStreams, Tables{nullptr, 1, &p, nullptr}))
         return fail(CEC_EINVAL, "internal: a launch's argument block cannot serve its patterns; not launched");
     return CEC_OK;
 }
@@ -971,7 +747,7 @@ struct RegionMemo {
     int dev = -1, key = -1;
     PatEntry *e = nullptr;  // pinned while memoised
     LaunchShape shape;
-    Pattern pat;            // the host copy (launch_combine's stream check)
+    Pattern pat;            // the host copy (the launch's stream check)
     ~RegionMemo() {
         if (e) pattern_done(e);
     }
@@ -997,7 +773,7 @@ static int region_launch(int dev, const void *src, int multby, size_t n, void *d
         std::vector<uint8_t> rows;
         if (int r = build_patterns({multiply_combo(multby, add, s_src, s_dst)}, 0, engine, pats, rows, true)) return r;
         PatEntry *e = nullptr;
-        if (int r = pattern_tables(dev, pats, rows, s, &e)) return r;
+        if (int r = pattern_tables(dev, pats.data(), pats.size(), &rows, s, &e)) return r;
         if (capturing) m = &once;           // (the cache marked the tables captured)
         else if (m->e) pattern_done(m->e);  // this launch's pin becomes the memo's
         m->dev = dev;
@@ -1006,11 +782,8 @@ static int region_launch(int dev, const void *src, int multby, size_t n, void *d
         m->shape = launch_shape(pats, nullptr);
         m->pat = pats[0];
     }
-    if (int rc = launch_combine(dev, st, Tables{m->e->d, 1, &m->pat, nullptr}, m->shape, engine == CEC_ENGINE_LDS,
-                                region, s, flags, released))
-        return rc;
-    HIP_TRY(hipGetLastError());
-    return CEC_OK;
+    return launch_combine(dev, st, Tables{m->e->d, 1, &m->pat, nullptr}, nullptr, m->shape, engine == CEC_ENGINE_LDS,
+                          region, s, false, flags, released);
 }
 
 CEC_API int cec_region_multiply(const void *src, int multby, size_t nbytes, void *dst, int add,

@@ -1,8 +1,7 @@
 // cec_scrub.inc -- device parity check: locate and repair bad 4 KiB units.
-// Included by cec_runtime.hip; not a separate TU.  scrub_launch is the library's second
-// launch routine beside launch_combine and is built from the same parts: a TileSource to
-// walk, pattern_tables for its coefficients, the launch_countdown hook, split_shift_for,
-// the capacity ladder and record_launch.  Only the kernel and its argument block differ.
+// Included by cec_runtime.hip; not a separate TU.  scrub_launch is built from the parts
+// launch_combine is: a TileSource to walk, a planner of cec_launchplan.hpp (plan_scrub) and
+// enqueue_launch.  Only the kernel and its argument block differ.
 //
 // Where the server would call it: the idle loop (idle_event_handler,
 // memcached.c:5712-5734) walks the arenas in idle time, and after a CEC_EHIP from
@@ -21,23 +20,22 @@
 namespace {
 
 constexpr uint32_t kScrubHead = 4;  // words before the per-tile words: [0] the counter (16-B aligned words)
-constexpr uint64_t kScrubMaxTiles = 0xFFFFFFFFull / kBlock;  // one dispatch: 64 GiB per arena
 
 template <int NT, int LT, bool kExact>
-void launch_scrub_k(const ScrubArgs &a, size_t lds, hipStream_t s) {
-    hipLaunchKernelGGL((scrub_kernel<NT, LT, kExact>), dim3(a.grid), dim3(kBlock >> a.split_shift), lds, s, a);
+void launch_scrub_k(const ScrubArgs &a, const LaunchPlan &lp, hipStream_t s) {
+    hipLaunchKernelGGL((scrub_kernel<NT, LT, kExact>), dim3(lp.grid), dim3(lp.block), lp.lds_bytes, s, a);
 }
 
-// The kernel of a launch over k data and lt parity streams: exact for the codes the suite
-// uses (only when the launch holds the code's every parity), else the capacity ladder's.
-Capacity launch_scrub(int k, int lt, bool whole_code, const ScrubArgs &a, size_t lds, hipStream_t s) {
-    if (whole_code && k == 3 && lt == 2) { launch_scrub_k<3, 2, true>(a, lds, s); return {3, 2}; }
-    if (whole_code && k == 4 && lt == 2) { launch_scrub_k<4, 2, true>(a, lds, s); return {4, 2}; }
-    if (whole_code && k == 6 && lt == 3) { launch_scrub_k<6, 3, true>(a, lds, s); return {6, 3}; }
-#define CEC_SG(NT, LT)                          \
-    launch_scrub_k<NT, LT, false>(a, lds, s);  \
-    return {NT, LT};
-    CEC_CAPACITY_RUNGS_FROM_4(k, lt, CEC_SG)
+// The kernel of a planned launch: `exact` (scrub_exact) one of the three compiled for the
+// codes the suite uses, else the plan's rung of the capacity ladder.
+void launch_scrub(bool exact, const ScrubArgs &a, const LaunchPlan &lp, hipStream_t s) {
+    if (exact && lp.nt == 3) return launch_scrub_k<3, 2, true>(a, lp, s);
+    if (exact && lp.nt == 4) return launch_scrub_k<4, 2, true>(a, lp, s);
+    if (exact) return launch_scrub_k<6, 3, true>(a, lp, s);
+#define CEC_SG(NT, LT)                           \
+    launch_scrub_k<NT, LT, false>(a, lp, s);    \
+    return;
+    CEC_CAPACITY_RUNGS_FROM_4(lp.nt, lp.lt, CEC_SG)
 #undef CEC_SG
 }
 
@@ -129,32 +127,37 @@ static std::vector<Pattern> scrub_patterns(const Code &code, int p0, int lt) {
 // One launch: parities [p0, p0 + lt) of the code against the k data streams.
 static int scrub_launch(int dev, cec_scrub_report *s, int k, int m, const int *matrix, const uint8_t *const *data,
                         const uint8_t *const *parity, int p0, int lt, const TileSource &src, hipStream_t stream) {
-    if (int rc = launch_countdown()) return rc;
     const std::vector<Pattern> pats = scrub_patterns(Code{k, m, matrix}, p0, lt);
+    const bool whole_code = p0 == 0 && lt == m;
     ScrubArgs a;
     memset(&a, 0, sizeof a);
-    Streams st;  // (for split_shift_for: every base of the launch)
-    for (int j = 0; j < k; ++j) a.base[st.add(data[j])] = data[j];
-    for (int l = 0; l < lt; ++l) a.base[st.add(parity[p0 + l])] = parity[p0 + l];
-    PatEntry *entry = nullptr;
-    if (int rc = pattern_tables(dev, pats, {}, stream, &entry)) return rc;
+    uintptr_t bases_or = 0;
+    for (int i = 0; i < k + lt; ++i) {
+        a.base[i] = i < k ? data[i] : parity[p0 + i - k];
+        bases_or |= reinterpret_cast<uintptr_t>(a.base[i]);
+    }
     a.tiles = src.tiles;
     a.implicit_len = src.implicit_len;
-    a.pattern = reinterpret_cast<const Pattern *>(entry->d);
     a.words = s->d_buf + kScrubHead;
     a.counter = s->d_buf;
     a.n_tiles = static_cast<uint32_t>(src.n_tiles);
-    a.split_shift = split_shift_for(st, src);
-    a.grid = static_cast<uint32_t>(src.n_tiles << a.split_shift);  // (n_tiles <= kScrubMaxTiles: fits)
     a.syn_shift = static_cast<uint32_t>(p0);
-    const size_t lds_bytes = occupancy_lds(dev, a.split_shift);
-    const Capacity cap = launch_scrub(k, lt, p0 == 0 && lt == m, a, lds_bytes, stream);
-    if (src.uses) src.uses->note(stream);
-    s->uses.note(stream);
-    pattern_done(entry);
-    HIP_TRY(hipGetLastError());
-    record_launch(CEC_KERNEL_SCRUB, cap, kAccAll, false, a.split_shift, 0, a.grid, src.n_tiles, lds_bytes);
-    return CEC_OK;
+    Launch l;
+    l.plan = plan_scrub(k, lt, whole_code, src.n_tiles, src.n_line_tiles, bases_or, g_knobs, waves_per_cu_cap(),
+                        g_dev[dev].lds_per_cu);
+    l.tb = Tables{nullptr, pats.size(), pats.data(), nullptr};
+    l.bases = a.base;
+    l.en = k;
+    l.el = lt;
+    l.uses[0] = src.uses;
+    l.uses[1] = &s->uses;
+    return enqueue_launch(dev, stream, l, [&](const LaunchPlan &lp, const uint8_t *d) {
+        a.pattern = reinterpret_cast<const Pattern *>(d);
+        a.split_shift = lp.split_shift;
+        a.grid = lp.grid;
+        launch_scrub(scrub_exact(k, lt, whole_code), a, lp, stream);
+        return CEC_OK;
+    });
 }
 
 // One launch of the digest check (cec_digest.inc), with scrub_launch's arguments.

@@ -28,7 +28,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from kernel_matrix_case import MUL  # noqa: E402
 
-TILE = 4096                  # kTile: tiles are cut at the 4 KiB boundaries of addr (append_tiles, cec_runtime.hip)
+TILE = 4096                  # kTile: tiles are cut at the 4 KiB boundaries of addr (append_tiles, cec_launchplan.hpp)
 SMALL_BYTES = 1 << 20        # kDrainSmallBytes (cec_drain.inc): the small window, 16-byte padded diffs
 SMALL_TILES = 8192           # kDrainSmallTiles (cec_drain.inc)
 ROUND_BYTES = 16 << 20       # kRoundBytes (cec_drain.inc): the pack path's pipelining granularity
@@ -96,7 +96,7 @@ def tile_half_of(staging_bytes: int) -> int:
 
 
 def tiles_of(addr: int, n: int) -> int:
-    """tiles_of (cec_runtime.hip): pieces of [addr, addr + n) that end on 4 KiB boundaries of addr."""
+    """tiles_of (cec_launchplan.hpp): pieces of [addr, addr + n) that end on 4 KiB boundaries of addr."""
     return (addr % TILE + n + TILE - 1) // TILE if n else 0
 
 

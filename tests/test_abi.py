@@ -363,3 +363,16 @@ def test_drain_wave_colouring(tmp_path):
     before it, one byte beyond, ending on its last byte) and the two parts a mixed batch is
     split into, on 2,000 random batches."""
     _run_hostplan_program(tmp_path, "waves_main")
+
+
+def test_launch_plan_decisions(tmp_path):
+    """Every decision of a kernel launch (cec_launchplan.hpp: which kernel a shape takes and
+    its capacity rung, the grid and the limits of one dispatch, the workgroup split, the store
+    policy and its write-through tail, the occupancy cap, the argument-block check, the tiles
+    of an extent, the knobs from the environment), included from the shipped header by
+    tests/drain_c/launch_plan_main.cpp and run under ASan + UBSan against the documented
+    rules as the program restates them: the (kind, nt, lt, acc) a combine launch can plan are
+    exactly the 4 + 40 + 12 kernels compiled per engine, grid x workgroup never passes
+    2^32 - 1, the scrub and digest limits hold at the limit and refuse one above it, and a
+    slot the block lacks or an empty base is refused at every input and output position."""
+    _run_hostplan_program(tmp_path, "launch_plan_main")

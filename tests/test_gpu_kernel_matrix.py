@@ -1,7 +1,8 @@
 """GPU: every compiled combine_kernel instantiation, and which one each op ran.
 
 Every operation of the library goes through one kernel template, compiled by
-launch_narrow / launch_exact / launch_generic (cec_runtime.hip) into 112 kernels: per
+launch_narrow / launch_exact / launch_generic (cec_runtime.hip; which one a launch takes
+is plan_combine's choice, cec_launchplan.hpp) into 112 kernels: per
 engine 4 narrow 1 x 1 kernels, 40 exact shapes and 12 capacity kernels, each with its own
 register allocation and unrolled code.  The parity tests compare bytes; these tests also
 read the launch record (cec_last_launch) after every launch, so a change of the dispatch

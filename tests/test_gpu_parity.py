@@ -963,7 +963,7 @@ def test_arena_allocator(gpu, oracle):
 @pytest.mark.parametrize("shift", [0, 1, 2])
 def test_forced_split_shift(gpu, oracle, shift):
     """Every workgroups-per-tile choice (1, 2, 4) is bit-exact on aligned, ragged and
-    misaligned tiles, not only the one the automatic rule picks (cec_runtime.hip
+    misaligned tiles, not only the one the automatic rule picks (cec_launchplan.hpp
     split_shift_for).  Child process: the library reads CEC_SPLIT_SHIFT once."""
     env = dict(os.environ, CEC_SPLIT_SHIFT=str(shift))
     r = subprocess.run(["python", os.path.join(ROOT, "tests", "split_case.py")], env=env,
