@@ -775,6 +775,116 @@ __global__ __launch_bounds__(kBlock) void digest_update_kernel(DigestUpdateArgs 
     }
 }
 
+// cec_digest_set: the live digests of a group kept current through the SET path, where the
+// diff is never stored: it is formed here from its two sources, d = new ^ old, and its ONE
+// digest is scattered to every array the SET changes,
+//     data_digests[j][u] ^= D        parity_digests[p][u] ^= MATRIX(k+p, j) * D.
+// digest_update_kernel's form: one wave per tile, four waves per workgroup, no LDS, no barrier.
+//   * lane L holds unit chunks L, L + 64, L + 128, L + 192 of d.  The new value is addressed
+//     from staging with the tile's src_off, the old bytes from data[j] with its arena offset;
+//     the two have independent alignment, so each source on its own takes one
+//     global_load_dwordx4 for a chunk that lies wholly inside the tile (16-B aligned address)
+//     or the byte gather over the covered bytes.  A chunk outside the tile is zero, and bytes
+//     outside the tile are never fetched from either source;
+//   * the wave's 32-byte total (digest_wave_total) is spread over ALL eight-lane groups, lane
+//     L holding dword L & 7; group L >> 3 serves destination slot L >> 3: slot 0 the data lid
+//     (coefficient 1), slot 1 + p parity p (patterns[p / 4]: coef[p % 4][j] / tab[p % 4][j],
+//     scalar loads; the multiply is a wave-uniform loop over the live slots with a per-lane
+//     select, 3 v_perm_b32 per slot);
+//   * ONE no-return global_atomic_xor, relaxed, agent scope, then carries eight slots, 32
+//     contiguous bytes per slot (RS(3,2): 24 active lanes); a ninth slot (m = 8 with the data
+//     digest) takes a second one.  A slot whose digest pointer is NULL or whose coefficient is
+//     0 is masked out; a tile with no slot left returns before it reads anything.
+struct DigestSetArgs {
+    const uint8_t *data[kPatN];         // data arenas: tiles' off counts from data[pattern]
+    const uint8_t *staging;             // tiles' src_off count from here
+    uint8_t *digests[kDigestArenas];    // [0, k): data lids; [k, k + m): parities; NULL: not kept
+    const Tile *tiles;
+    const Pattern *patterns;            // [p / 4]: coef / tab[p % 4][j] = MATRIX(k + p, j)
+    uint32_t n_tiles;
+    uint32_t k, m;
+};
+
+// Chunk `pos` of a unit whose byte 0 would lie at `unit`: its covered bytes [b0, b1) only.
+__device__ inline uint4 ld_covered(const uint8_t *unit, bool aligned, uint32_t pos, uint32_t b0, uint32_t b1) {
+    return aligned && b1 - b0 == 16u ? ld16(unit, pos) : gather16_at(unit, pos, b0 - pos, b1 - b0);
+}
+
+__global__ __launch_bounds__(kBlock) void digest_set_kernel(DigestSetArgs a) {
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t t = (blockIdx.x << 2) + wave;
+    if (t >= a.n_tiles) return;  // (wave-uniform)
+    const CEC_CONST Tile *tl = as_const(a.tiles) + t;
+    const uint64_t off = tl->off;
+    const uint32_t len = tl->len;
+    const uint32_t src = tl->pattern;
+    const CEC_CONST Pattern *P = as_const(a.patterns);
+    // the destination slots of this tile (wave-uniform): bit 0 the data lid, bit 1 + p parity p
+    uint32_t live = a.digests[src] != nullptr ? 1u : 0u;
+#pragma unroll
+    for (uint32_t p = 0; p < 8; ++p)  // (CEC_MAX_M)
+        if (p < a.m && a.digests[a.k + p] != nullptr && P[p >> 2].coef[p & 3][src] != 0) live |= 2u << p;
+    if (live == 0) return;  // nothing kept: nothing read
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t lo = static_cast<uint32_t>(off) & (kTile - 1u), hi = lo + len;  // the tile in its unit
+    // where unit byte 0 would lie in each source: only bytes [lo, hi) of it are addressed
+    const uint8_t *nu = a.staging + tl->src_off - lo;
+    const uint8_t *old = a.data[src] + off - lo;
+    const bool nu_al = (reinterpret_cast<uint64_t>(nu) & 15) == 0;
+    const bool old_al = (reinterpret_cast<uint64_t>(old) & 15) == 0;
+
+    uint4 c[4];
+    if (nu_al && old_al && len == kTile) {
+        uint4 x[4], y[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) x[j] = ld16(nu, (lane + 64u * j) * 16u);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) y[j] = ld16(old, (lane + 64u * j) * 16u);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) c[j] = make_uint4(x[j].x ^ y[j].x, x[j].y ^ y[j].y, x[j].z ^ y[j].z, x[j].w ^ y[j].w);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t pos = (lane + 64u * j) * 16u;
+            const uint32_t b0 = max(pos, lo), b1 = min(pos + 16u, hi);  // covered bytes of the chunk
+            c[j] = make_uint4(0, 0, 0, 0);
+            if (b0 < b1) {
+                const uint4 x = ld_covered(nu, nu_al, pos, b0, b1);
+                const uint4 y = ld_covered(old, old_al, pos, b0, b1);
+                c[j] = make_uint4(x.x ^ y.x, x.y ^ y.y, x.z ^ y.z, x.w ^ y.w);
+            }
+        }
+    }
+    uint32_t d[8];
+    digest_wave_total(c, lane, d);
+    uint32_t v = 0;  // dword lane & 7 of the total, in every lane
+#pragma unroll
+    for (int w = 0; w < 8; ++w) {
+        const uint32_t total = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(d[w]), 63));
+        v = (lane & 7u) == static_cast<uint32_t>(w) ? total : v;
+    }
+    const PermEngine::Sel sel = PermEngine::sel(v);
+    const uint64_t at = (off >> 12) * kDigestBytes + (lane & 7u) * 4u;
+#pragma unroll 1
+    for (uint32_t base = 0; (live >> base) != 0; base += 8) {  // (one round; two for nine slots)
+        uint32_t x = 0;
+        uintptr_t to = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < 8; ++q) {
+            const uint32_t slot = base + q;  // (wave-uniform)
+            if (((live >> slot) & 1u) == 0) continue;
+            const uint32_t p = slot - 1u;    // the parity of a slot >= 1
+            const uint32_t prod = slot == 0 ? v : PermEngine::mul(sel, P[p >> 2].tab[p & 3][src], nullptr);
+            const uintptr_t dst = reinterpret_cast<uintptr_t>(a.digests[slot == 0 ? src : a.k + p]);
+            const bool mine = (lane >> 3) == q;
+            x = mine ? prod : x;
+            to = mine ? dst : to;
+        }
+        if (to != 0)
+            __hip_atomic_fetch_xor((CEC_GLOBAL uint32_t *)(to + at), x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 // cec_scrub_digests: the scrub's syndrome and ratio test on the digests.  The digest is
 // linear and commutes with scalars, so digest(S_p) is the syndrome of the digests and
 // digest(ratio * S_0 ^ S_q) their ratio test: the report word has cec_scrub's exact meaning

@@ -423,6 +423,17 @@ static LaunchPlan plan_digest_update(uint64_t n_tiles) {
     return p;
 }
 
+// A digest set (the SET path's digest launch): one wave per tile, four per workgroup; each
+// wave reads two sources, the staged value and the data arena's old bytes.
+static LaunchPlan plan_digest_set(uint64_t n_tiles) {
+    LaunchPlan p = plan_start(CEC_KERNEL_DIGEST_SET, n_tiles, kDigestMaxWork);
+    if (p.refusal != kPlanOk) return p;
+    p.nt = 2;
+    p.acc = kAccAll;
+    p.grid = static_cast<uint32_t>((n_tiles + 3) / 4);
+    return p;
+}
+
 // A digest check of lt parities against k data digests: one lane per unit, as many units
 // as a scrub report holds tiles.
 static LaunchPlan plan_digest_check(int k, int lt, uint64_t n_units) {

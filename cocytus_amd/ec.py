@@ -120,6 +120,7 @@ CEC_KERNEL_SCRUB = 3  # cec_scrub's read-only kernel
 CEC_KERNEL_DIGEST = 4  # cec_digest's reduction (nt = the arenas of the launch, lt = 0)
 CEC_KERNEL_DIGEST_CHECK = 5  # cec_scrub_digests: the scrub's test, one lane per unit
 CEC_KERNEL_DIGEST_UPDATE = 6  # cec_digest_apply_diffs: one wave per tile into the live digests
+CEC_KERNEL_DIGEST_SET = 7  # cec_digest_set: new ^ old of a SET batch into the digests of every arena it changes
 DIGEST_BYTES = 32  # CEC_DIGEST_BYTES: per 4 KiB unit
 CEC_SCRUB_UNLOCATED = -1
 
@@ -231,6 +232,8 @@ _SIGS = {
     "cec_scrub_digests": ([_vp, _i, _i, _ip, _pp, _pp, _vp, _vp], _i),
     "cec_scrub_digests_region": ([_vp, _i, _i, _ip, _pp, _pp, ctypes.c_size_t, _vp], _i),
     "cec_digest_apply_diffs": ([_i, _i, _ip, _i, _vp, _vp, ctypes.c_uint64, _vp, _vp], _i),
+    "cec_digest_set": ([_i, _i, _ip, _pp, _vp, _pp, _pp, ctypes.c_uint64, _vp, _vp], _i),
+    "cec_diff_update_digests": ([_i, _i, _ip, _pp, _vp, _pp, _i, _pp, _pp, ctypes.c_uint64, _vp, _vp], _i),
     "cec_digest_verify_region": ([_vp, _vp, _vp, ctypes.c_size_t, _vp], _i),
     "cec_drainer_set_digests": ([_vp, _vp, ctypes.c_uint64], _i),
     "cec_cache_get_info": ([ctypes.POINTER(CacheInfo)], _i),
@@ -631,6 +634,30 @@ def digest_apply_diffs(k, m, matrix, lid_self, diffs, digests, n_units: int, pla
     stream.  Overlapping extents are accepted."""
     _check(lib().cec_digest_apply_diffs(k, m, _int_array(matrix), lid_self, _ptr(diffs), _ptr(digests), n_units,
                                         plan.handle, _stream(stream)))
+
+
+def _ptr_array_or_null(xs):
+    return None if xs is None else _ptr_array(xs)
+
+
+def digest_set(k, m, matrix, data, staging, data_digests, parity_digests, n_units: int, plan: Plan,
+               stream=None) -> None:
+    """cec_digest_set: fold new ^ old of the plan's SETs (diff_update's extents) into the live
+    digest arrays of the arenas the batch would change; touches no arena; async on stream.
+    data_digests (k) / parity_digests (m) may be None, and so may any entry: not kept."""
+    _check(lib().cec_digest_set(k, m, _int_array(matrix), _ptr_array_or_null(data), _ptr(staging),
+                                _ptr_array_or_null(data_digests), _ptr_array_or_null(parity_digests), n_units,
+                                plan.handle, _stream(stream)))
+
+
+def diff_update_digests(k, m, matrix, data, staging, parity, install: bool, data_digests, parity_digests,
+                        n_units: int, plan: Plan, stream=None) -> None:
+    """cec_diff_update_digests: diff_update with the live digests of every arena it writes kept
+    current (the digest launch, then diff_update's own, on one stream)."""
+    _check(lib().cec_diff_update_digests(k, m, _int_array(matrix), _ptr_array_or_null(data), _ptr(staging),
+                                         _ptr_array_or_null(parity), int(bool(install)), _ptr_array_or_null(data_digests),
+                                         _ptr_array_or_null(parity_digests), n_units, plan.handle,
+                                         _stream(stream)))
 
 
 def recovery_mask(k: int, m: int, leader_lid: int, connected: Sequence[int]) -> int:

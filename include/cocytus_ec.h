@@ -164,7 +164,8 @@ int cec_encode_region(int k, int m, const int *matrix, const uint8_t *const *dat
  * j = pattern: d = staging[src_off..] ^ data[j][off..]; parity[p][off..] ^=
  * MATRIX(k+p, j) * d for every p with parity[p] != NULL (a lost parity is
  * skipped, memcached.c:2692-2694); if install, data[j][off..] = new value
- * (memcached.c:5666).  Extents must not overlap (CEC_EOVERLAP). */
+ * (memcached.c:5666).  Extents must not overlap (CEC_EOVERLAP).  Live unit digests of
+ * the arenas are not kept by this op: cec_diff_update_digests (LIVE DIGESTS) keeps them. */
 int cec_diff_update(int k, int m, const int *matrix, uint8_t *const *data,
                     const uint8_t *staging, uint8_t *const *parity, int install,
                     const cec_plan *plan, void *stream);
@@ -664,8 +665,14 @@ int cec_scrub_repair(cec_scrub_report *s, int k, int m, const int *matrix, uint8
  *     the own arena).  A mismatch is bit rot or a stray write in that arena;
  *   - across processes, no arena read: cec_scrub_digests over the shards' live arrays (same
  *     SNAPSHOT RULE).  It catches what the local check cannot: a lost or twice-applied diff.
+ * With all k + m arenas on one device the SET path keeps them too: cec_diff_update_digests
+ * (below) is cec_diff_update with the digests of every arena it writes kept current, from one
+ * pass over new ^ old and no diff buffer.  Plain cec_diff_update does not keep digests.
+ * The digests of a full-stripe encode need no arena read either: cec_encode_region over the k
+ * data digest arrays as data and the m parity digest arrays as parity, len = 32 * units,
+ * yields the parity digests by linearity.
  * An op that writes an arena outside this path -- cec_scrub_repair, the recovery pool's
- * solves into arenas, cec_diff_update (its fused path does not keep digests), and the units
+ * solves into arenas, a cec_diff_update that was not cec_diff_update_digests, and the units
  * of a drain window after a CEC_EHIP -- is followed by a re-base of the units it wrote:
  * cec_digest_region of the one arena `arena + 4096 * u0` into `digests + 32 * u0`, len =
  * 4096 * n, for units [u0, u0 + n) (to the arena's end for the last, ragged unit); the unit
@@ -725,6 +732,56 @@ int cec_scrub_digests_region(cec_scrub_report *s, int k, int m, const int *matri
  * ENGINE: PERM arithmetic, as cec_digest. */
 int cec_digest_apply_diffs(int k, int m, const int *matrix, int lid_self, const uint8_t *diffs,
                            uint8_t *digests, uint64_t n_units, const cec_plan *plan, void *stream);
+
+/* Fold the diff a SET batch would make into the live digests; touches no arena.  One launch,
+ * async on `stream`.  The plan's extents are cec_diff_update's: `off` the arena offset,
+ * `src_off` the offset into `staging`, `pattern` the source data lid j.  For every 4 KiB tile
+ *     D = digest(a 4 KiB unit, zero but for (staging[src_off ..] ^ data[j][off ..]) at off & 4095)
+ *     data_digests[j][off >> 12]   ^= D
+ *     parity_digests[p][off >> 12] ^= MATRIX(k+p, j) * D      for p in 0..m-1
+ * data_digests (k entries) and parity_digests (m entries) are live arrays of n_units units
+ * each (the geometry of cec_digest_region).  Either array of pointers may be NULL, and so may
+ * any entry: that array is not kept.  A destination whose coefficient is 0 is skipped as
+ * well, and a tile with no destination left reads nothing.  Arena and staging bytes are only
+ * read, and never outside the tiles; the two sources may have any alignment, each on its own
+ * (16-byte aligned ones take the wide path).  The totals go in with relaxed agent-scope
+ * atomic XORs, as in cec_digest_apply_diffs.
+ * The op reads the old bytes, so it describes the batch only BEFORE the batch is installed,
+ * and an extent that overlaps another would read bytes the batch itself replaces: a plan
+ * whose extents overlap is CEC_EOVERLAP (unlike cec_digest_apply_diffs).  While arenas and
+ * staging are unchanged, running it twice restores the digests.
+ * Refused with CEC_EINVAL before anything is launched, the message naming the offender: a
+ * bad code, NULL data, staging or plan, a NULL data[j] (j < k), a non-NULL digest array that
+ * is not 16-byte aligned, an extent pattern >= k, a plan of another device, n_units above
+ * 2^52, an extent that ends beyond n_units * 4096, and more than 67,108,860 tiles.  An empty
+ * plan launches nothing.  A failed launch (CEC_EHIP) changes no digest.
+ * ENGINE: PERM arithmetic whatever cec_set_engine says; cec_last_engine() reports PERM. */
+int cec_digest_set(int k, int m, const int *matrix, const uint8_t *const *data,
+                   const uint8_t *staging, uint8_t *const *data_digests,
+                   uint8_t *const *parity_digests, uint64_t n_units,
+                   const cec_plan *plan, void *stream);
+
+/* cec_diff_update, with the digests of every arena it writes kept current: the SET op of a
+ * placement with all k + m arenas on one device.  Every check of cec_diff_update and of
+ * cec_digest_set is made, and both steps are planned, before anything is launched.  The op
+ * is strict about the arrays: data_digests[j] must be non-NULL for every j < k when install
+ * != 0, and parity_digests[p] for every p with parity[p] != NULL, else CEC_EINVAL -- a
+ * silently stale array is worse than a refusal.  It then enqueues on `stream`
+ *   1. the cec_digest_set launch, over the parity digests of the live parities and, when
+ *      install != 0, the data digests (install == 0 leaves the data arenas as they are, so
+ *      their digests are not touched); a lost parity (parity[p] == NULL) is skipped;
+ *   2. behind it, cec_diff_update itself, unchanged: one launch per four outputs (one for
+ *      m + install <= 4).  Arena bytes after the op are cec_diff_update's, on either engine.
+ * If step 2 fails before its first launch (CEC_EHIP) the arenas and staging are untouched,
+ * so the op enqueues the digest launch once more, which restores the digests, and returns
+ * CEC_EHIP: arenas and digests are then as before the call.  If that restoring launch fails
+ * too, or step 2 failed after one of its launches ran (m + install > 4), the message says
+ * that the digests of the plan's units are uncertain: re-base them with cec_digest_region
+ * as LIVE DIGESTS describes. */
+int cec_diff_update_digests(int k, int m, const int *matrix, uint8_t *const *data,
+                            const uint8_t *staging, uint8_t *const *parity, int install,
+                            uint8_t *const *data_digests, uint8_t *const *parity_digests,
+                            uint64_t n_units, const cec_plan *plan, void *stream);
 
 /* A process's check of itself: compare its live array with a fresh cec_digest_region of its
  * own arena (both device arrays of 32 B per unit over [0, len), 16-byte aligned).  It is
@@ -795,7 +852,10 @@ enum { CEC_KERNEL_NARROW = 0, CEC_KERNEL_EXACT = 1, CEC_KERNEL_GENERIC = 2,
                                     * acc = CEC_ACC_ALL, PERM, flags 0 */,
        CEC_KERNEL_DIGEST_UPDATE = 6 /* cec_digest_apply_diffs and the drainer's digest launch: nt = 1,
                                      * lt = 0, acc = CEC_ACC_ALL, split_shift 0, PERM, flags 0, grid =
-                                     * ceil(tiles / 4) */ };
+                                     * ceil(tiles / 4) */,
+       CEC_KERNEL_DIGEST_SET = 7 /* cec_digest_set and the digest launch of cec_diff_update_digests:
+                                  * nt = 2 (the staged value and the old bytes), lt = 0, acc =
+                                  * CEC_ACC_ALL, split_shift 0, PERM, flags 0, grid = ceil(tiles / 4) */ };
 enum { CEC_ACC_NONE = 0, CEC_ACC_ALL = 1, CEC_ACC_ALL_BUT_LAST = 2, CEC_ACC_RUNTIME = 3 };
 enum { CEC_LAUNCH_SYS_RELEASE = 1, CEC_LAUNCH_WRITE_THROUGH = 2,
        CEC_LAUNCH_WT_TAIL = 4 /* non-temporal body, write-through stores from work item wt_from on */ };
