@@ -13,9 +13,13 @@
 // with a fresh one through the same check.  With the whole group on one device the SET path
 // keeps them: cec_digest_set folds new ^ old of a batch into the digests of every arena the
 // batch changes, and cec_diff_update_digests runs it ahead of cec_diff_update.
+// The bulk paths keep them in the launch that moves the bytes: cec_encode_digests,
+// cec_encode_region_digests and cec_decode_digests run the encode's and the decode's
+// combinations (encode_combo, decode_combos) through run_combos_digests, whose kernel emits
+// the digest of every unit it reads and writes.
 // Built from the library's parts: a TileSource to walk, the planners of cec_launchplan.hpp
-// (plan_digest, plan_digest_update, plan_digest_set, plan_digest_check), scrub_patterns for the check's
-// coefficients, enqueue_launch.
+// (plan_digest, plan_digest_update, plan_digest_set, plan_combine_digest, plan_digest_check),
+// scrub_patterns for the check's coefficients, enqueue_launch.
 
 namespace {
 
@@ -280,6 +284,193 @@ CEC_API int cec_diff_update_digests(int k, int m, const int *matrix, uint8_t *co
                         "of the plan's units are uncertain: re-base them with cec_digest_region of arena + 4096 * u "
                         "into digests + 32 * u", op, why);
     return fail(rc, "%s: cec_diff_update failed (%s); arenas and digests are as before the call", op, why);
+}
+
+// ---- digest-emitting combinations: cec_encode_digests, cec_decode_digests ----
+static_assert(CEC_KERNEL_COMBINE_DIGEST == 8, "cec_launch_record::kind");
+
+// The live digest arrays of a launch's streams: dig[slot] goes with Streams::base[slot]
+// (NULL: that stream's digests are not kept).
+struct DigestSlots {
+    uint8_t *dig[kMaxStreams] = {};
+};
+
+// The plan's output capacity: combine_digest_kernel<1>, <2> or <4> (three instantiations).
+static void launch_combine_digest(const CombineDigestArgs &a, const LaunchPlan &lp, hipStream_t s) {
+    if (lp.lt == 1) hipLaunchKernelGGL(combine_digest_kernel<1>, dim3(lp.grid), dim3(lp.block), 0, s, a);
+    else if (lp.lt == 2) hipLaunchKernelGGL(combine_digest_kernel<2>, dim3(lp.grid), dim3(lp.block), 0, s, a);
+    else hipLaunchKernelGGL(combine_digest_kernel<4>, dim3(lp.grid), dim3(lp.block), 0, s, a);
+}
+
+// run_combos for the digest-emitting kernel, for any list of combinations whose outputs are
+// all written (kModeWrite): one launch per kPatL outputs, as build_patterns splits them, each
+// writing its outputs' bytes and their digests together; the inputs' digests go with the first
+// launch only.  Every tile of `src` must obey the unit rule (the caller checks it: it knows
+// the arena length).  Everything is checked, built and planned before the first launch, so a
+// refusal launches nothing; always the PERM engine.
+static int run_combos_digests(const char *op, int dev, const Streams &st, const DigestSlots &dg,
+                              const std::vector<Combo> &combos, const TileSource &src, hipStream_t stream) {
+    t_last_engine = CEC_ENGINE_PERM;  // whatever cec_set_engine says
+    size_t max_out = 0;
+    int max_in = 0;
+    bool in_digests = false;
+    for (const Combo &c : combos) {
+        max_out = std::max(max_out, c.outs.size());
+        max_in = std::max(max_in, c.n_in);
+        for (const Combo::Out &o : c.outs)
+            if (o.mode != kModeWrite)
+                return fail(CEC_EINVAL, "internal: %s: a read-modify-write output in a digest-emitting launch; "
+                                        "not launched", op);
+        for (int i = 0; i < std::min(c.n_in, static_cast<int>(kPatN)); ++i) in_digests |= dg.dig[c.in_stream[i]] != nullptr;
+    }
+    // (a launch of its own for the inputs' digests where nothing is produced: every parity lost)
+    const size_t groups = std::max<size_t>((max_out + kPatL - 1) / kPatL, in_digests ? 1 : 0);
+    if (src.n_tiles == 0 || groups == 0) return CEC_OK;  // (before the fail hook counts)
+    struct Group {
+        std::vector<Pattern> pats;
+        LaunchPlan plan;
+        DigestSlots dig;
+        bool in_digests = false;
+    };
+    std::vector<Group> gs(groups);
+    for (size_t g = 0; g < groups; ++g) {
+        Group &G = gs[g];
+        std::vector<uint8_t> rows;  // (PERM: none)
+        if (int r = build_patterns(combos, g, CEC_ENGINE_PERM, G.pats, rows)) return r;
+        int lt = 0;
+        for (size_t q = 0; q < combos.size(); ++q) {
+            const Pattern &p = G.pats[q];
+            lt = std::max(lt, p.n_out);
+            for (int l = 0; l < p.n_out; ++l) G.dig.dig[p.out_stream[l]] = dg.dig[p.out_stream[l]];
+            for (int i = 0; g == 0 && i < p.n_in; ++i) G.dig.dig[p.in_stream[i]] = dg.dig[p.in_stream[i]];
+        }
+        G.in_digests = g == 0 && in_digests;
+        G.plan = plan_combine_digest(max_in, lt, src.n_tiles);
+        if (G.plan.refusal == kPlanTooLarge)
+            return fail(CEC_EINVAL, "%s: %llu tiles, one launch holds %llu", op,
+                        static_cast<unsigned long long>(src.n_tiles), static_cast<unsigned long long>(kDigestMaxWork));
+        if (G.plan.refusal != kPlanOk)
+            return fail(CEC_EINVAL, "internal: %s: no digest-emitting kernel for %d x %d; not launched", op, max_in, lt);
+    }
+    for (Group &G : gs) {
+        Launch l;
+        l.plan = G.plan;
+        if (st.refused) l.plan.refusal = kPlanStreams;
+        l.tb = Tables{nullptr, G.pats.size(), G.pats.data(), nullptr};
+        l.bases = st.base;
+        l.en = G.plan.nt;
+        l.el = G.plan.lt;
+        l.uses[0] = src.uses;  // a plan's streams, for its destroy
+        const int rc = enqueue_launch(dev, stream, l, [&](const LaunchPlan &lp, const uint8_t *d) {
+            CombineDigestArgs a;
+            memset(&a, 0, sizeof a);
+            for (int i = 0; i < kMaxStreams; ++i) {
+                a.base[i] = st.base[i];
+                a.dig[i] = G.dig.dig[i];
+            }
+            a.tiles = src.tiles;
+            a.implicit_len = src.implicit_len;
+            a.patterns = reinterpret_cast<const Pattern *>(d);
+            a.n_tiles = static_cast<uint32_t>(lp.n_tiles);  // (<= kDigestMaxWork)
+            a.in_digests = G.in_digests;
+            launch_combine_digest(a, lp, stream);
+            return CEC_OK;
+        });
+        if (rc) return rc;
+    }
+    return CEC_OK;
+}
+
+// A digest array an op was handed: NULL (not kept) or 16-byte aligned.
+static int digest_array_ok(const char *op, const char *what, int i, const uint8_t *d) {
+    if (reinterpret_cast<uintptr_t>(d) & 15) return fail(CEC_EINVAL, "%s: %s[%d] is not 16-byte aligned", op, what, i);
+    return CEC_OK;
+}
+
+// The unit rule (cec_launchplan.hpp) on what an op walks: the plan's tiles, or the region
+// [0, len) of an arena of arena_len bytes.
+static int unit_rule_ok(const char *op, const cec_plan *plan, uint64_t len, uint64_t arena_len) {
+    if (!plan) {
+        if (const UnitBreach b = unit_rule_region(len, arena_len))
+            return fail(CEC_EINVAL, "%s: the region [0, %llu) %s (arena_len %llu)", op, static_cast<unsigned long long>(len),
+                        unit_breach_text(b), static_cast<unsigned long long>(arena_len));
+        return CEC_OK;
+    }
+    size_t bad = 0;
+    if (const UnitBreach b = unit_rule_tiles(plan->h_tiles.data(), plan->h_tiles.size(), arena_len, &bad))
+        return fail(CEC_EINVAL, "%s: the tile at offset %llu, %u bytes, %s (arena_len %llu): every extent must "
+                                "be whole 4096-byte units", op, static_cast<unsigned long long>(plan->h_tiles[bad].off),
+                    plan->h_tiles[bad].len, unit_breach_text(b), static_cast<unsigned long long>(arena_len));
+    return CEC_OK;
+}
+
+static int encode_digests_common(const char *op, int k, int m, const int *matrix, const uint8_t *const *data,
+                                 uint8_t *const *parity, uint8_t *const *data_digests,
+                                 uint8_t *const *parity_digests, uint64_t arena_len, const cec_plan *plan, uint64_t len,
+                                 void *stream) {
+    if (int r = check_code(k, m, matrix)) return r;
+    if (!data || !parity) return fail(CEC_EINVAL, "%s: NULL arena array", op);
+    int dev;
+    if (int r = current_device(&dev)) return r;
+    EncodeCombo e;
+    if (int r = encode_combo(op, Code{k, m, matrix}, data, parity, &e)) return r;
+    DigestSlots dg;
+    for (int j = 0; j < k && data_digests; ++j) {
+        if (int r = digest_array_ok(op, "data_digests", j, data_digests[j])) return r;
+        dg.dig[e.s_data[j]] = data_digests[j];
+    }
+    for (int p = 0; p < m && parity_digests; ++p) {
+        if (!parity[p]) continue;  // a lost parity: its digest entry is ignored
+        if (int r = digest_array_ok(op, "parity_digests", p, parity_digests[p])) return r;
+        dg.dig[e.s_parity[p]] = parity_digests[p];
+    }
+    TileSource src;
+    if (int r = plan ? TileSource::of_plan(plan, dev, &src) : TileSource::of_region(len, &src)) return r;
+    if (int r = unit_rule_ok(op, plan, len, arena_len)) return r;
+    return run_combos_digests(op, dev, e.st, dg, {e.c}, src, static_cast<hipStream_t>(stream));
+}
+
+CEC_API int cec_encode_digests(int k, int m, const int *matrix, const uint8_t *const *data, uint8_t *const *parity,
+                               uint8_t *const *data_digests, uint8_t *const *parity_digests, uint64_t arena_len,
+                               const cec_plan *plan, void *stream) {
+    if (!plan) return fail(CEC_EINVAL, "cec_encode_digests: plan is NULL");
+    if (int r = single_pattern_plan(plan, "cec_encode_digests")) return r;
+    return encode_digests_common("cec_encode_digests", k, m, matrix, data, parity, data_digests, parity_digests,
+                                 arena_len, plan, 0, stream);
+}
+
+CEC_API int cec_encode_region_digests(int k, int m, const int *matrix, const uint8_t *const *data,
+                                      uint8_t *const *parity, uint8_t *const *data_digests,
+                                      uint8_t *const *parity_digests, size_t len, void *stream) {
+    return encode_digests_common("cec_encode_region_digests", k, m, matrix, data, parity, data_digests,
+                                 parity_digests, len, nullptr, len, stream);
+}
+
+CEC_API int cec_decode_digests(int k, int m, const int *matrix, const uint32_t *masks, int n_masks,
+                               const uint8_t *const *arenas, uint8_t *const *out, uint8_t *const *out_digests,
+                               uint64_t arena_len, const cec_plan *plan, void *stream) {
+    const char *op = "cec_decode_digests";
+    if (int r = check_code(k, m, matrix)) return r;
+    if (!masks || n_masks < 1 || !arenas || !out || !plan) return fail(CEC_EINVAL, "%s: bad args", op);
+    int dev;
+    if (int r = current_device(&dev)) return r;
+    if (plan->n_ext && plan->max_pattern >= static_cast<uint32_t>(n_masks))
+        return fail(CEC_EINVAL, "%s: an extent names mask %u of %d", op, plan->max_pattern, n_masks);
+    DecodeCombos d;
+    if (int r = decode_combos(op, Code{k, m, matrix}, masks, n_masks, arenas, out, &d)) return r;
+    // strict about the arrays: every lid the op rebuilds has its digests emitted
+    DigestSlots dg;
+    for (int j = 0; j < k; ++j) {
+        if (!(d.lost & (1u << j))) continue;
+        if (!out_digests || !out_digests[j])
+            return fail(CEC_EINVAL, "%s: out_digests[%d] is NULL and a mask loses lid %d", op, j, j);
+        if (int r = digest_array_ok(op, "out_digests", j, out_digests[j])) return r;
+        dg.dig[d.s_out[j]] = out_digests[j];
+    }
+    TileSource src;
+    if (int r = TileSource::of_plan(plan, dev, &src)) return r;
+    if (int r = unit_rule_ok(op, plan, 0, arena_len)) return r;
+    return run_combos_digests(op, dev, d.st, dg, d.combos, src, static_cast<hipStream_t>(stream));
 }
 
 // One launch: the digests of parities [p0, p0 + lt) against the k data digests, one lane

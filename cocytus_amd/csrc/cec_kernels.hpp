@@ -885,6 +885,147 @@ __global__ __launch_bounds__(kBlock) void digest_set_kernel(DigestSetArgs a) {
     }
 }
 
+// cec_encode_digests / cec_decode_digests: a combination whose launch also emits the unit
+// digests of the streams it holds, so the bulk paths keep live digests without reading an
+// arena twice.  The digest kernels' geometry, not combine_kernel's split: one wave per whole
+// 4 KiB unit, four waves per workgroup, no LDS, no barrier, no atomics, one workgroup per
+// four tiles and no grid-stride (the host refuses more tiles than one dispatch holds).
+//   * lane L holds chunks L, L + 64, L + 128, L + 192 of the unit (digest_wave_total's
+//     layout) of ONE input at a time: the pattern's n_in inputs are walked in a wave-uniform
+//     loop, each accumulated as coef * x into the outputs' accumulators with the PERM
+//     arithmetic (tables from Pattern::tab, scalar loads).  Registers: 4 uint4 of input and
+//     4 uint4 per output, whatever k is; LT is the output capacity, the pattern's n_out the
+//     runtime count.  Outputs are written (kModeWrite), never read;
+//   * a stream on its own takes four global_load_dwordx4 / non-temporal st16 for a full unit
+//     at a 16-B aligned address, else gather16 / scatter16 with the valid count: bytes past
+//     the tile's len read 0, are never fetched and are never stored;
+//   * every stream slot whose dig[] pointer is non-NULL, input or output, gets the digest of
+//     the four chunks the lane holds of it (digest_wave_total); the wave's last lane writes
+//     the 32 bytes at dig[slot] + 32 * (off >> 12) with two plain 16-byte stores, as
+//     digest_kernel ends.  The bytes digested are the bytes loaded or stored, in registers.
+struct CombineDigestArgs {
+    uint8_t *base[kMaxStreams];
+    uint8_t *dig[kMaxStreams];  // parallel to base[]: the stream's live digest array (16-B aligned); NULL: not kept
+    const Tile *tiles;          // NULL: implicit region [0, implicit_len), pattern 0
+    const Pattern *patterns;
+    uint64_t implicit_len;
+    uint32_t n_tiles;
+    uint32_t in_digests;        // some input slot has a digest: a tile without outputs still reads
+};
+
+// The byte gather / scatter of a misaligned or ragged unit derives 64 byte offsets and lane
+// masks from len alone.  They are the same for every stream of a tile, so the compiler would
+// compute them once ahead of the input loop and hold them across it, and the full units'
+// path would pay for them in registers (242 VGPRs against 60 with one output).  An opaque copy of len
+// where the rare path begins keeps them local to it.
+__device__ inline uint32_t rare_path(uint32_t len) {
+    __asm__ volatile("" : "+s"(len));
+    return len;
+}
+// The unit at `p`, this lane's four chunks; bytes from len on read 0 and are not fetched.
+__device__ inline void load_unit(const uint8_t *p, uint32_t lane, uint32_t len, uint4 (&c)[4]) {
+    if ((reinterpret_cast<uint64_t>(p) & 15) == 0 && len == kTile) {  // (wave-uniform)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) c[j] = ld16(p, (lane + 64u * j) * 16u);
+    } else {
+        len = rare_path(len);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t pos = (lane + 64u * j) * 16u;
+            c[j] = make_uint4(0, 0, 0, 0);
+            if (pos < len) c[j] = gather16(p, pos, min(16u, len - pos));
+        }
+    }
+}
+// ... and its store: the first len bytes of the unit, nothing past them.
+__device__ inline void store_unit(uint8_t *p, uint32_t lane, uint32_t len, const uint4 (&c)[4]) {
+    if ((reinterpret_cast<uint64_t>(p) & 15) == 0 && len == kTile) {  // (wave-uniform)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) st16(p, (lane + 64u * j) * 16u, c[j]);
+    } else {
+        len = rare_path(len);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t pos = (lane + 64u * j) * 16u;
+            if (pos < len) scatter16(p, pos, min(16u, len - pos), c[j]);
+        }
+    }
+}
+// The digest of the unit in c[] to dig + 32 * unit (every lane of the wave must be active).
+__device__ inline void emit_digest(uint8_t *dig, uint64_t unit, const uint4 (&c)[4], uint32_t lane) {
+    uint32_t d[8];
+    digest_wave_total(c, lane, d);
+    if (lane == 63) {
+        CEC_GLOBAL u32x4 *o = (CEC_GLOBAL u32x4 *)((uintptr_t)dig + unit * kDigestBytes);
+        u32x4 v0, v1;
+        v0.x = d[0]; v0.y = d[1]; v0.z = d[2]; v0.w = d[3];
+        v1.x = d[4]; v1.y = d[5]; v1.z = d[6]; v1.w = d[7];
+        o[0] = v0;
+        o[1] = v1;
+    }
+}
+
+template <int LT>
+__global__ __launch_bounds__(kBlock) void combine_digest_kernel(CombineDigestArgs a) {
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t t = (blockIdx.x << 2) + wave;
+    if (t >= a.n_tiles) return;  // (wave-uniform)
+    const uint32_t lane = threadIdx.x & 63u;
+    const TileRef tr = load_tile(a, t);
+    const CEC_CONST Pattern *P = as_const(a.patterns) + tr.pattern;
+    const int n_in = P->n_in;
+    const int n_out = min(P->n_out, LT);
+    if (n_out == 0 && a.in_digests == 0) return;  // nothing written, nothing kept: nothing read
+    const uint64_t unit = tr.off >> 12;
+    // base[] and dig[] are indexed by a slot the pattern names: read them from the kernarg
+    // segment with scalar loads (indexing the by-value copy selects among all 96 pointers)
+    const CEC_CONST CombineDigestArgs *ka = (const CEC_CONST CombineDigestArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+
+    uint4 acc[LT][4];
+#pragma unroll
+    for (int l = 0; l < LT; ++l)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[l][j] = make_uint4(0, 0, 0, 0);
+
+#pragma unroll 1
+    for (int i = 0; i < n_in; ++i) {
+        const int slot = P->in_stream[i];
+        uint4 c[4];
+        load_unit(ka->base[slot] + (P->in_src[i] ? tr.src_off : tr.off), lane, tr.len, c);
+#pragma unroll
+        for (int l = 0; l < LT; ++l) {
+            if (l >= n_out) continue;
+            const int cf = P->coef[l][i];
+            if (cf == 0) continue;
+            const CEC_CONST uint32_t *tb = P->tab[l][i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (cf == 1) {
+                    acc[l][j].x ^= c[j].x;
+                    acc[l][j].y ^= c[j].y;
+                    acc[l][j].z ^= c[j].z;
+                    acc[l][j].w ^= c[j].w;
+                } else {
+                    acc[l][j].x ^= PermEngine::mul(PermEngine::sel(c[j].x), tb, nullptr);
+                    acc[l][j].y ^= PermEngine::mul(PermEngine::sel(c[j].y), tb, nullptr);
+                    acc[l][j].z ^= PermEngine::mul(PermEngine::sel(c[j].z), tb, nullptr);
+                    acc[l][j].w ^= PermEngine::mul(PermEngine::sel(c[j].w), tb, nullptr);
+                }
+            }
+        }
+        uint8_t *dg = ka->dig[slot];
+        if (dg != nullptr) emit_digest(dg, unit, c, lane);
+    }
+#pragma unroll
+    for (int l = 0; l < LT; ++l) {
+        if (l >= n_out) continue;
+        const int slot = P->out_stream[l];
+        store_unit(ka->base[slot] + (P->out_src[l] ? tr.src_off : tr.off), lane, tr.len, acc[l]);
+        uint8_t *dg = ka->dig[slot];
+        if (dg != nullptr) emit_digest(dg, unit, acc[l], lane);
+    }
+}
+
 // cec_scrub_digests: the scrub's syndrome and ratio test on the digests.  The digest is
 // linear and commutes with scalars, so digest(S_p) is the syndrome of the digests and
 // digest(ratio * S_0 ^ S_q) their ratio test: the report word has cec_scrub's exact meaning

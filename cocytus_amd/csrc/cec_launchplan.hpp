@@ -434,6 +434,66 @@ static LaunchPlan plan_digest_set(uint64_t n_tiles) {
     return p;
 }
 
+// A digest-emitting combination (cec_encode_digests, cec_decode_digests): one wave per whole
+// unit, four per workgroup, no grid-stride.  `n_in`: the most inputs a pattern of the launch
+// has (the kernel walks them in a loop: no input capacity); `lt`: the most outputs, run by the
+// output capacity 1, 2 or 4 above it (a launch that only digests its inputs has lt = 0 and runs
+// capacity 1).
+static int combine_digest_capacity(int lt) { return lt <= 1 ? 1 : lt <= 2 ? 2 : 4; }
+static LaunchPlan plan_combine_digest(int n_in, int lt, uint64_t n_tiles) {
+    LaunchPlan p = plan_start(CEC_KERNEL_COMBINE_DIGEST, n_tiles, kDigestMaxWork);
+    if (p.refusal == kPlanOk && (n_in < 0 || n_in > kPatN || lt < 0 || lt > kPatL)) p.refusal = kPlanNoKernel;
+    if (p.refusal != kPlanOk) return p;
+    p.nt = n_in;
+    p.lt = combine_digest_capacity(lt);
+    p.grid = static_cast<uint32_t>((n_tiles + 3) / 4);
+    return p;
+}
+
+// The unit rule of the digest-emitting ops.  The digest of a partly written unit cannot be
+// formed without its old bytes, so every tile of such an op is a whole 4 KiB unit at a 4 KiB
+// arena offset; the one exception is the arena's own ragged last unit, a tile shorter than
+// 4 KiB that ends exactly at arena_len (its digest is that of the bytes zero-padded, as
+// cec_digest_region forms it).  No tile ends beyond arena_len.  Tiles are append_tiles' pieces
+// of the extents, so the rule on them is the rule on the extents: an extent at a 4 KiB offset
+// yields whole units and at most a short last tile, any other offset a misplaced first tile.
+enum UnitBreach {
+    kUnitOk = 0,
+    kUnitOffset,   // the tile does not start on a 4 KiB arena boundary
+    kUnitPartial,  // shorter than a unit and not the end of the arena
+    kUnitBeyond,   // ends beyond arena_len
+};
+static UnitBreach unit_rule_tile(uint64_t off, uint32_t len, uint64_t arena_len) {
+    if (off % kTile != 0) return kUnitOffset;
+    if (off > arena_len || len > arena_len - off) return kUnitBeyond;
+    if (len != kTile && off + len != arena_len) return kUnitPartial;
+    return kUnitOk;
+}
+// The first tile that breaks the rule (*bad), or kUnitOk.
+static UnitBreach unit_rule_tiles(const Tile *t, size_t n, uint64_t arena_len, size_t *bad) {
+    for (size_t i = 0; i < n; ++i)
+        if (const UnitBreach b = unit_rule_tile(t[i].off, t[i].len, arena_len)) {
+            if (bad) *bad = i;
+            return b;
+        }
+    return kUnitOk;
+}
+// The implicit region [0, len) of an arena of arena_len bytes: whole units, and a short last
+// one only where the region is the whole arena.
+static UnitBreach unit_rule_region(uint64_t len, uint64_t arena_len) {
+    if (len > arena_len) return kUnitBeyond;
+    if (len % kTile != 0 && len != arena_len) return kUnitPartial;
+    return kUnitOk;
+}
+static const char *unit_breach_text(UnitBreach b) {
+    switch (b) {
+    case kUnitOffset: return "does not start on a 4096-byte arena boundary";
+    case kUnitPartial: return "is a partial unit that does not end at arena_len";
+    case kUnitBeyond: return "ends beyond arena_len";
+    default: return "is a whole unit";
+    }
+}
+
 // A digest check of lt parities against k data digests: one lane per unit, as many units
 // as a scrub report holds tiles.
 static LaunchPlan plan_digest_check(int k, int lt, uint64_t n_units) {
@@ -450,7 +510,9 @@ static LaunchPlan plan_digest_check(int k, int lt, uint64_t n_units) {
 // The layout check of a planned launch: `bases` is the stream array of the argument block
 // its kernel is passed, which has as many slots as the kernel's kind says.
 static void check_layout(LaunchPlan &p, const uint8_t *const *bases, const Tables &tb) {
-    const int slots = p.kind == kKindNarrow ? kNarrowStreams : p.kind <= kKindGeneric ? kMaxStreams : kScrubStreams;
+    const int slots = p.kind == kKindNarrow ? kNarrowStreams
+                      : p.kind <= kKindGeneric || p.kind == CEC_KERNEL_COMBINE_DIGEST ? kMaxStreams
+                                                                                      : kScrubStreams;
     if (p.refusal == kPlanOk && !stream_layout_ok(bases, slots, tb)) p.refusal = kPlanLayout;
 }
 

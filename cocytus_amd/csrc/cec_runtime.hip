@@ -810,6 +810,28 @@ static bool large_values(const cec_plan *plan) {
     return !plan || plan->total >= (uint64_t(64) << 10) * static_cast<uint64_t>(std::max(plan->n_ext, 1));
 }
 
+// The full-stripe encode as a combination, stated once for cec_encode / cec_encode_region and
+// their digest-emitting forms: the k data arenas in, every live parity out.
+struct EncodeCombo {
+    Streams st;
+    Combo c;
+    int s_data[CEC_MAX_K], s_parity[CEC_MAX_M];  // the slot of each lid's arena
+};
+static int encode_combo(const char *op, const Code &code, const uint8_t *const *data, uint8_t *const *parity,
+                        EncodeCombo *out) {
+    for (int j = 0; j < code.k; ++j) {
+        if (!data[j]) return fail(CEC_EINVAL, "%s: data[%d] is NULL", op, j);
+        out->c.in(out->s_data[j] = out->st.add(data[j]));
+    }
+    for (int p = 0; p < code.m; ++p) {
+        const int slot = out->s_parity[p] = out->st.add(parity[p]);
+        if (!parity[p]) continue;  // a lost parity is simply not produced
+        Combo::Out &o = out->c.out(slot, kModeWrite);
+        for (int j = 0; j < code.k; ++j) o.coef[j] = code.at(code.k + p, j);
+    }
+    return CEC_OK;
+}
+
 static int encode_common(int k, int m, const int *matrix, const uint8_t *const *data,
                          uint8_t *const *parity, const cec_plan *plan, uint64_t len,
                          void *stream) {
@@ -817,21 +839,10 @@ static int encode_common(int k, int m, const int *matrix, const uint8_t *const *
     if (!data || !parity) return fail(CEC_EINVAL, "cec_encode: NULL arena array");
     int dev;
     if (int r = current_device(&dev)) return r;
-    const Code code{k, m, matrix};
-    Streams st;
-    Combo c;
-    for (int j = 0; j < k; ++j) {
-        if (!data[j]) return fail(CEC_EINVAL, "cec_encode: data[%d] is NULL", j);
-        c.in(st.add(data[j]));
-    }
-    for (int p = 0; p < m; ++p) {
-        const int slot = st.add(parity[p]);
-        if (!parity[p]) continue;  // a lost parity is simply not produced
-        Combo::Out &o = c.out(slot, kModeWrite);
-        for (int j = 0; j < k; ++j) o.coef[j] = code.at(k + p, j);
-    }
+    EncodeCombo e;
+    if (int r = encode_combo("cec_encode", Code{k, m, matrix}, data, parity, &e)) return r;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return plan ? run_combos_plan(dev, st, {c}, plan, s) : run_combos_region(dev, st, {c}, len, s);
+    return plan ? run_combos_plan(dev, e.st, {e.c}, plan, s) : run_combos_region(dev, e.st, {e.c}, len, s);
 }
 
 // Ops with one pattern index every tile's pattern field into a one-entry table: it must be 0.
@@ -985,6 +996,45 @@ CEC_API int cec_solve(int k, int m, const int *matrix, uint32_t mask,
     return run_combos_plan(dev, st, {c}, plan, static_cast<hipStream_t>(stream));
 }
 
+// The decode as combinations, one per mask, stated once for cec_decode and cec_decode_digests:
+// the k lids of the mask in, the data lids it loses out.
+struct DecodeCombos {
+    Streams st;
+    std::vector<Combo> combos;
+    int s_arena[CEC_MAX_K + CEC_MAX_M], s_out[CEC_MAX_K];  // the slot of each lid's arena / output
+    uint32_t lost = 0;                                     // the data lids some mask loses
+};
+static int decode_combos(const char *op, const Code &code, const uint32_t *masks, int n_masks,
+                         const uint8_t *const *arenas, uint8_t *const *out, DecodeCombos *d) {
+    const int k = code.k, m = code.m;
+    Streams &st = d->st;
+    for (int lid = 0; lid < k + m; ++lid) d->s_arena[lid] = st.add(arenas[lid]);
+    for (int j = 0; j < k; ++j) d->s_out[j] = st.add(out[j]);
+    d->combos.assign(n_masks, Combo());
+    for (int q = 0; q < n_masks; ++q) {
+        const uint32_t mask = masks[q];
+        Loss ls;
+        if (int r = Loss::of(code, mask, op, &ls)) return r;
+        Combo &c = d->combos[q];
+        // inputs: the n participating parities, then the k-n surviving data shards
+        for (int i = 0; i < k; ++i) {
+            const int lid = i < ls.n ? ls.pars[i] : ls.surv[i - ls.n];
+            if (!arenas[lid]) return fail(CEC_EINVAL, "%s: arena %d (in mask 0x%x) is NULL", op, lid, mask);
+            c.in(d->s_arena[lid]);
+        }
+        // D_lost[x] = sum_r inv[x][r] * (P_r ^ sum_s M[P_r][s] * D_s)
+        for (int x = 0; x < ls.n; ++x) {
+            if (!out[ls.lost[x]]) return fail(CEC_EINVAL, "%s: out[%d] is NULL", op, ls.lost[x]);
+            d->lost |= 1u << ls.lost[x];
+            Combo::Out &o = c.out(d->s_out[ls.lost[x]], kModeWrite);
+            for (int r = 0; r < ls.n; ++r) o.coef[r] = ls.at(x, r);
+            for (int s = 0; s < ls.n_surv; ++s)
+                for (int r = 0; r < ls.n; ++r) o.coef[ls.n + s] ^= gf_mul(ls.at(x, r), code.at(ls.pars[r], ls.surv[s]));
+        }
+    }
+    return CEC_OK;
+}
+
 CEC_API int cec_decode(int k, int m, const int *matrix, const uint32_t *masks, int n_masks,
                        const uint8_t *const *arenas, uint8_t *const *out, const cec_plan *plan,
                        void *stream) {
@@ -995,36 +1045,12 @@ CEC_API int cec_decode(int k, int m, const int *matrix, const uint32_t *masks, i
     if (int r = current_device(&dev)) return r;
     if (plan->n_ext && plan->max_pattern >= static_cast<uint32_t>(n_masks))
         return fail(CEC_EINVAL, "cec_decode: an extent names mask %u of %d", plan->max_pattern, n_masks);
-    const Code code{k, m, matrix};
-    Streams st;
-    int s_arena[CEC_MAX_K + CEC_MAX_M], s_out[CEC_MAX_K];
-    for (int lid = 0; lid < k + m; ++lid) s_arena[lid] = st.add(arenas[lid]);
-    for (int j = 0; j < k; ++j) s_out[j] = st.add(out[j]);
-    std::vector<Combo> combos(n_masks);
-    for (int q = 0; q < n_masks; ++q) {
-        const uint32_t mask = masks[q];
-        Loss ls;
-        if (int r = Loss::of(code, mask, "cec_decode", &ls)) return r;
-        Combo &c = combos[q];
-        // inputs: the n participating parities, then the k-n surviving data shards
-        for (int i = 0; i < k; ++i) {
-            const int lid = i < ls.n ? ls.pars[i] : ls.surv[i - ls.n];
-            if (!arenas[lid]) return fail(CEC_EINVAL, "cec_decode: arena %d (in mask 0x%x) is NULL", lid, mask);
-            c.in(s_arena[lid]);
-        }
-        // D_lost[x] = sum_r inv[x][r] * (P_r ^ sum_s M[P_r][s] * D_s)
-        for (int x = 0; x < ls.n; ++x) {
-            if (!out[ls.lost[x]]) return fail(CEC_EINVAL, "cec_decode: out[%d] is NULL", ls.lost[x]);
-            Combo::Out &o = c.out(s_out[ls.lost[x]], kModeWrite);
-            for (int r = 0; r < ls.n; ++r) o.coef[r] = ls.at(x, r);
-            for (int s = 0; s < ls.n_surv; ++s)
-                for (int r = 0; r < ls.n; ++r) o.coef[ls.n + s] ^= gf_mul(ls.at(x, r), code.at(ls.pars[r], ls.surv[s]));
-        }
-    }
+    DecodeCombos d;
+    if (int r = decode_combos("cec_decode", Code{k, m, matrix}, masks, n_masks, arenas, out, &d)) return r;
     // AUTO: values of 64 KiB and more (large_values) run the LDS engine, ahead of PERM by a
     // median 3 % there (rotating or one mask: configs[4]'s 1 MiB D1-by-P1 rebuild +4.9 %);
     // 4 KiB values run PERM (rotating masks -1.7 %, one mask +1.1 %: within 2 %)
-    return run_combos_plan(dev, st, combos, plan, static_cast<hipStream_t>(stream), large_values(plan));
+    return run_combos_plan(dev, d.st, d.combos, plan, static_cast<hipStream_t>(stream), large_values(plan));
 }
 
 CEC_API uint32_t cec_recovery_mask(int k, int m, int leader_lid, const int *connected) {

@@ -121,6 +121,7 @@ CEC_KERNEL_DIGEST = 4  # cec_digest's reduction (nt = the arenas of the launch, 
 CEC_KERNEL_DIGEST_CHECK = 5  # cec_scrub_digests: the scrub's test, one lane per unit
 CEC_KERNEL_DIGEST_UPDATE = 6  # cec_digest_apply_diffs: one wave per tile into the live digests
 CEC_KERNEL_DIGEST_SET = 7  # cec_digest_set: new ^ old of a SET batch into the digests of every arena it changes
+CEC_KERNEL_COMBINE_DIGEST = 8  # cec_encode_digests / cec_decode_digests: a combination that emits its units' digests
 DIGEST_BYTES = 32  # CEC_DIGEST_BYTES: per 4 KiB unit
 CEC_SCRUB_UNLOCATED = -1
 
@@ -234,6 +235,9 @@ _SIGS = {
     "cec_digest_apply_diffs": ([_i, _i, _ip, _i, _vp, _vp, ctypes.c_uint64, _vp, _vp], _i),
     "cec_digest_set": ([_i, _i, _ip, _pp, _vp, _pp, _pp, ctypes.c_uint64, _vp, _vp], _i),
     "cec_diff_update_digests": ([_i, _i, _ip, _pp, _vp, _pp, _i, _pp, _pp, ctypes.c_uint64, _vp, _vp], _i),
+    "cec_encode_digests": ([_i, _i, _ip, _pp, _pp, _pp, _pp, ctypes.c_uint64, _vp, _vp], _i),
+    "cec_encode_region_digests": ([_i, _i, _ip, _pp, _pp, _pp, _pp, ctypes.c_size_t, _vp], _i),
+    "cec_decode_digests": ([_i, _i, _ip, ctypes.POINTER(_u32), _i, _pp, _pp, _pp, ctypes.c_uint64, _vp, _vp], _i),
     "cec_digest_verify_region": ([_vp, _vp, _vp, ctypes.c_size_t, _vp], _i),
     "cec_drainer_set_digests": ([_vp, _vp, ctypes.c_uint64], _i),
     "cec_cache_get_info": ([ctypes.POINTER(CacheInfo)], _i),
@@ -339,7 +343,7 @@ def kernel_disassembly(path: str | None = None) -> dict[str, list[str]] | None:
             cur = funcs.setdefault(m.group(1), [])
         elif cur is not None and line.startswith("\t"):
             ins = line.split("//")[0].strip()
-            if ins:
+            if ins and ins != "...":  # ("...": objdump's mark for the zero padding behind a kernel)
                 cur.append(ins)
     return funcs or None
 
@@ -658,6 +662,36 @@ def diff_update_digests(k, m, matrix, data, staging, parity, install: bool, data
                                          _ptr_array_or_null(parity), int(bool(install)), _ptr_array_or_null(data_digests),
                                          _ptr_array_or_null(parity_digests), n_units, plan.handle,
                                          _stream(stream)))
+
+
+def encode_digests(k, m, matrix, data, parity, data_digests, parity_digests, arena_len: int, plan: Plan,
+                   stream=None) -> None:
+    """cec_encode_digests: encode, and in the same launches the digests of the plan's units of
+    the data arenas (data_digests, k) and the parities (parity_digests, m); either may be None,
+    and so may any entry: not kept.  Every extent is whole 4 KiB units of an arena of arena_len
+    bytes (a short last one only at its end)."""
+    _check(lib().cec_encode_digests(k, m, _int_array(matrix), _ptr_array_or_null(data), _ptr_array_or_null(parity),
+                                    _ptr_array_or_null(data_digests), _ptr_array_or_null(parity_digests), arena_len,
+                                    plan.handle, _stream(stream)))
+
+
+def encode_region_digests(k, m, matrix, data, parity, data_digests, parity_digests, length: int,
+                          stream=None) -> None:
+    """cec_encode_region_digests: encode_digests over the implicit 4 KiB tiling of [0, length),
+    length being the arena length."""
+    _check(lib().cec_encode_region_digests(k, m, _int_array(matrix), _ptr_array_or_null(data),
+                                           _ptr_array_or_null(parity), _ptr_array_or_null(data_digests),
+                                           _ptr_array_or_null(parity_digests), length, _stream(stream)))
+
+
+def decode_digests(k, m, matrix, masks: Sequence[int], arenas, out, out_digests, arena_len: int, plan: Plan,
+                   stream=None) -> None:
+    """cec_decode_digests: decode, and in the same launches the digests of the rebuilt units
+    into out_digests (k entries by data lid; the entry of every lid some mask loses is required)."""
+    marr = (ctypes.c_uint32 * len(masks))(*[int(x) for x in masks])
+    _check(lib().cec_decode_digests(k, m, _int_array(matrix), marr, len(masks), _ptr_array_or_null(arenas),
+                                    _ptr_array_or_null(out), _ptr_array_or_null(out_digests), arena_len,
+                                    plan.handle, _stream(stream)))
 
 
 def recovery_mask(k: int, m: int, leader_lid: int, connected: Sequence[int]) -> int:

@@ -668,15 +668,37 @@ int cec_scrub_repair(cec_scrub_report *s, int k, int m, const int *matrix, uint8
  * With all k + m arenas on one device the SET path keeps them too: cec_diff_update_digests
  * (below) is cec_diff_update with the digests of every arena it writes kept current, from one
  * pass over new ^ old and no diff buffer.  Plain cec_diff_update does not keep digests.
- * The digests of a full-stripe encode need no arena read either: cec_encode_region over the k
- * data digest arrays as data and the m parity digest arrays as parity, len = 32 * units,
- * yields the parity digests by linearity.
- * An op that writes an arena outside this path -- cec_scrub_repair, the recovery pool's
- * solves into arenas, a cec_diff_update that was not cec_diff_update_digests, and the units
- * of a drain window after a CEC_EHIP -- is followed by a re-base of the units it wrote:
- * cec_digest_region of the one arena `arena + 4096 * u0` into `digests + 32 * u0`, len =
- * 4096 * n, for units [u0, u0 + n) (to the arena's end for the last, ragged unit); the unit
- * geometry makes that pointer arithmetic valid.
+ * The bulk paths keep them as well: cec_encode_digests / cec_encode_region_digests and
+ * cec_decode_digests (below) are cec_encode / cec_encode_region / cec_decode whose launches
+ * also emit the digests of the units they read and write, from the bytes in registers, so
+ * basing a group and rebuilding a lost shard need no second pass over any arena.
+ * The ops that still write an arena outside this path, and are followed by a re-base of the
+ * units they wrote, are: cec_scrub_repair (it rewrites partial tiles), cec_solve, the
+ * recovery sessions' and the recovery pool's solves into arenas, a plain cec_encode /
+ * cec_encode_region / cec_decode / cec_diff_update (the forms without _digests; an encode or
+ * decode over extents that are not whole units has no other form: the _digests ops refuse
+ * them), and the units of a drain window after a CEC_EHIP.  A re-base is cec_digest_region of the one arena
+ * `arena + 4096 * u0` into `digests + 32 * u0`, len = 4096 * n, for units [u0, u0 + n) (to
+ * the arena's end for the last, ragged unit); the unit geometry makes that pointer arithmetic
+ * valid.
+ *
+ * VERIFIED RECOVERY: the digest is linear, so the digest of every rebuilt unit is predictable
+ * from the survivors' live digest arrays alone, and cec_decode_digests emits the digest of the
+ * bytes it actually wrote.  The recipe, for units [u0, u0 + n) rebuilt under mask index q:
+ *   1. take the survivors' live digest arrays (the k lids of the mask);
+ *   2. cec_decode over them as "arenas", with a plan of the extent {off = 32 * u0, len = 32 * n,
+ *      pattern = q} (one per run of units with the same mask), into a predicted array per lost
+ *      lid;
+ *   3. cec_decode_digests over the arenas, which rebuilds the units and emits their digests
+ *      into an emitted array per lost lid;
+ *   4. cec_digest_verify_region(report, predicted + 32 * u0, emitted + 32 * u0, 4096 * n), then
+ *      cec_scrub_wait.
+ * A unit that differs means: in that unit some survivor's bytes no longer match its live
+ * digest (bit rot, a stray write, a lost diff), so the rebuilt unit was computed from bytes
+ * the group never agreed on and is not to be trusted -- found before the shard is served, at
+ * no extra arena read.  (Every decoding coefficient of an MDS code is non-zero, so a changed
+ * survivor digest always changes the prediction.)  LIMIT: the digest's own, above -- corruption
+ * of three or more chunks of one unit that lies in the digest's null space is not seen.
  *
  * cec_digest: digests[a] + 32 * t = digest of tile t of arenas[a], for n arenas (1..24: a
  * whole group, or a process's own) in one launch; async on `stream`.  Read-only on the
@@ -783,6 +805,60 @@ int cec_diff_update_digests(int k, int m, const int *matrix, uint8_t *const *dat
                             uint8_t *const *data_digests, uint8_t *const *parity_digests,
                             uint64_t n_units, const cec_plan *plan, void *stream);
 
+/* Digest-emitting encode and decode: the bulk paths with live digests kept (LIVE DIGESTS,
+ * VERIFIED RECOVERY above).  cec_encode / cec_encode_region / cec_decode on the same
+ * arguments, and in the same launches the digests of the units read and written: one wave per
+ * 4 KiB unit holds the unit of each stream in registers, so no arena byte is read twice.
+ * ARENA BYTES after each op are those of the op without _digests, on either engine setting.
+ * DIGESTS: arrays of cec_digest_region's geometry (unit u of the arena at array + 32 * u,
+ * 16-byte aligned).  For every unit u of the plan (unit off >> 12 of each tile), array[u] of
+ * every kept array equals what cec_digest_region of that arena yields for unit u afterwards;
+ * units outside the plan are not touched in any array.
+ *   cec_encode_digests / cec_encode_region_digests keep data_digests (k entries, the inputs)
+ *   and parity_digests (m entries, the outputs).  Either array of pointers may be NULL, and so
+ *   may any entry: that array is not kept.  A lost parity (parity[p] == NULL) is not produced
+ *   and its digest entry is ignored.  In cec_encode_region_digests, len is the arena length.
+ *   cec_decode_digests keeps out_digests (k entries, indexed by data lid like `out`): the
+ *   digests of the rebuilt units.  The entry of every lid that some mask loses must be
+ *   non-NULL, else CEC_EINVAL -- strictness where staleness would be silent, as in
+ *   cec_diff_update_digests.  Masks rotate per extent through `pattern`, as in cec_decode.
+ * UNIT RULE: the digest of a partly written unit cannot be formed without its old bytes, so
+ * every extent has off % 4096 == 0 and every tile is a whole 4 KiB unit, except a last tile
+ * shorter than 4096 bytes, accepted only where it ends exactly at arena_len (the arena's own
+ * ragged last unit: its digest is that of the bytes zero-padded); no extent ends beyond
+ * arena_len.
+ * LAUNCHES: one per four outputs (CEC_KERNEL_COMBINE_DIGEST), in order on `stream`; input
+ * digests are written by the first launch only.  Every launch writes a unit's bytes and that
+ * unit's digests together.  FAILURE: after a CEC_EHIP on launch g, the outputs of the launches
+ * before g are complete with matching digests, and the outputs of g and of later launches are
+ * untouched in bytes and in digests (the input digests are complete if g > 0, untouched if
+ * g == 0); cec_last_launch's seq tells how many ran.
+ * REFUSED with CEC_EINVAL before anything is launched, the message naming the offender:
+ * everything cec_encode / cec_decode refuse, a non-NULL digest array that is not 16-byte
+ * aligned, a breach of the unit rule, an out_digests entry missing for a lost lid, and more
+ * than 67,108,860 tiles (one dispatch).  An empty plan or len == 0 launches nothing and
+ * returns CEC_OK.
+ * ENGINE: PERM arithmetic whatever cec_set_engine says; cec_last_engine() reports PERM.
+ * COST: by byte counts, basing an RS(3,2) group moves 5/8 of the traffic of cec_encode_region
+ * + cec_digest_region over the data + an encode over the digest arrays, and a rebuild 4/5 of
+ * cec_decode + cec_digest of the rebuilt units.  MEASURED on one MI355X, 65,536 units per
+ * arena, HIP events, fused and unfused interleaved in one process, three processes
+ * (tools/fused_digest_bench.py, profiles/fused_digest_bench.jsonl): basing
+ * takes 0.66 of the unfused sequence's time (219-221 us against 334-337 us), the rebuild with
+ * masks rotating per unit 0.84-0.86 (189-190 us against 220-226 us).  The ops' reason is
+ * their consistency contract; the time saved comes with it. */
+int cec_encode_digests(int k, int m, const int *matrix, const uint8_t *const *data,
+                       uint8_t *const *parity, uint8_t *const *data_digests,
+                       uint8_t *const *parity_digests, uint64_t arena_len,
+                       const cec_plan *plan, void *stream);
+int cec_encode_region_digests(int k, int m, const int *matrix, const uint8_t *const *data,
+                              uint8_t *const *parity, uint8_t *const *data_digests,
+                              uint8_t *const *parity_digests, size_t len, void *stream);
+int cec_decode_digests(int k, int m, const int *matrix, const uint32_t *masks, int n_masks,
+                       const uint8_t *const *arenas, uint8_t *const *out,
+                       uint8_t *const *out_digests, uint64_t arena_len,
+                       const cec_plan *plan, void *stream);
+
 /* A process's check of itself: compare its live array with a fresh cec_digest_region of its
  * own arena (both device arrays of 32 B per unit over [0, len), 16-byte aligned).  It is
  * cec_scrub_digests_region with the code k = 1, m = 1, matrix {1, 1}, `fresh` as the data
@@ -855,7 +931,10 @@ enum { CEC_KERNEL_NARROW = 0, CEC_KERNEL_EXACT = 1, CEC_KERNEL_GENERIC = 2,
                                      * ceil(tiles / 4) */,
        CEC_KERNEL_DIGEST_SET = 7 /* cec_digest_set and the digest launch of cec_diff_update_digests:
                                   * nt = 2 (the staged value and the old bytes), lt = 0, acc =
-                                  * CEC_ACC_ALL, split_shift 0, PERM, flags 0, grid = ceil(tiles / 4) */ };
+                                  * CEC_ACC_ALL, split_shift 0, PERM, flags 0, grid = ceil(tiles / 4) */,
+       CEC_KERNEL_COMBINE_DIGEST = 8 /* cec_encode_digests, cec_encode_region_digests, cec_decode_digests:
+                                      * nt = the launch's inputs, lt = the output capacity {1,2,4}, acc =
+                                      * CEC_ACC_NONE, split_shift 0, PERM, flags 0, grid = ceil(tiles / 4) */ };
 enum { CEC_ACC_NONE = 0, CEC_ACC_ALL = 1, CEC_ACC_ALL_BUT_LAST = 2, CEC_ACC_RUNTIME = 3 };
 enum { CEC_LAUNCH_SYS_RELEASE = 1, CEC_LAUNCH_WRITE_THROUGH = 2,
        CEC_LAUNCH_WT_TAIL = 4 /* non-temporal body, write-through stores from work item wt_from on */ };
